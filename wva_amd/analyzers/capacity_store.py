@@ -366,7 +366,10 @@ class CapacityStorePersistence:
         self.namespace = namespace
         self.write_interval_seconds = write_interval_seconds
         self.analyzer = analyzer  # optional: k2 history rides along
-        self._last_write = 0.0
+        # never written yet: time.monotonic() has no defined epoch (it can
+        # be seconds after boot), so 0.0 would delay the first write by
+        # up to a full interval on a freshly started host
+        self._last_write = float("-inf")
         self._last_payload = ""
 
     def restore(self) -> int:
