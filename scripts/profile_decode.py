@@ -23,7 +23,21 @@ def main():
     p.add_argument("--iters", type=int, default=10)
     p.add_argument("--context", type=int, default=512)
     p.add_argument("--model", default="8b", choices=["8b", "tiny"])
+    p.add_argument("--mixtral", default=None, choices=["calibrate", "ab"],
+                   help="run the Mixtral-8x7B section instead: `calibrate` "
+                        "writes calibration_mixtral[_IMPL].json, `ab` the "
+                        "grouped-vs-baseline ITL table")
+    p.add_argument("--moe-impl", default="auto",
+                   choices=["auto", "dense", "sparse", "grouped"],
+                   help="expert-MLP path for --mixtral calibrate")
+    p.add_argument("--out-dir", default="profile_out",
+                   help="directory the --mixtral sections write into")
     args = p.parse_args()
+
+    if args.mixtral == "calibrate":
+        return calibrate_mixtral(args.moe_impl, args.out_dir)
+    if args.mixtral == "ab":
+        return mixtral_grouped_ab(out_dir=args.out_dir)
 
     import torch
     from wva_amd.calibration.model import LLAMA_3_8B, TINY, LlamaDecodeModel
@@ -52,10 +66,6 @@ def main():
         f"decode: batch={args.batch} ctx={args.context} iters={args.iters} "
         f"ITL={itl_ms:.3f} ms  decode_tps={args.batch / (itl_ms / 1000.0):.0f}"
     )
-
-
-if __name__ == "__main__":
-    main()
 
 
 def attn_bench():
@@ -111,9 +121,10 @@ def calibrate_70b():
         f.write(result.to_json())
 
 
-def calibrate_mixtral():
+def calibrate_mixtral(moe_impl="auto", out_dir="profile_out"):
     """Mixtral-8x7B (MoE) on ONE MI355X: ~94 GB bf16 weights resident
-    (BASELINE config #4's second model family)."""
+    (BASELINE config #4's second model family). `moe_impl` selects the
+    expert-MLP path (MixtralDecodeModel) and is recorded in the JSON."""
     import json
     import time as _t
 
@@ -123,7 +134,8 @@ def calibrate_mixtral():
     from wva_amd.calibration.moe_model import MIXTRAL_8X7B, MixtralDecodeModel
 
     batches = [1, 8, 32, 64]
-    model = MixtralDecodeModel(MIXTRAL_8X7B, max_batch=max(batches), max_seq=1024)
+    model = MixtralDecodeModel(MIXTRAL_8X7B, max_batch=max(batches),
+                               max_seq=1024, moe_impl=moe_impl)
     itls = []
     for b in batches:
         model.reset(b, 512)
@@ -139,6 +151,7 @@ def calibrate_mixtral():
     alpha, beta, r2 = fit_itl_curve(batches, itls)
     rec = {
         "model": MIXTRAL_8X7B.name,
+        "moe_impl": moe_impl,
         "gpu_count": 1,
         "alpha_ms": alpha,
         "beta_ms": beta,
@@ -153,9 +166,78 @@ def calibrate_mixtral():
     print("mixtral calibration:", json.dumps(rec, indent=2))
     import os
 
-    os.makedirs("gpurun_out", exist_ok=True)
-    with open("gpurun_out/calibration_mixtral.json", "w") as f:
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if moe_impl == "auto" else f"_{moe_impl}"
+    name = f"calibration_mixtral{suffix}.json"
+    with open(os.path.join(out_dir, name), "w") as f:
         json.dump(rec, f, indent=2)
+
+
+def mixtral_grouped_ab(batches=(1, 2, 4, 8, 16, 32, 64, 128, 256), iters=8,
+                       out_dir="profile_out"):
+    """Mixtral-8x7B ITL(B) at ctx 512: the grouped expert MLP against the
+    path `auto` takes at that batch (dense ≤ 64, sparse above), one model
+    instance, same box. Steps are hipGraph-captured wherever the path can
+    be captured — the sparse path syncs with the host per expert and
+    cannot, so it is timed eagerly. Writes the profile JSON (which records
+    the impl that produced it) and an A/B table."""
+    import json
+    import os
+
+    from wva_amd.calibration.itl_benchmark import fit_itl_curve, measure_itl
+    from wva_amd.calibration.moe_model import MIXTRAL_8X7B, MixtralDecodeModel
+
+    batches = list(batches)
+    model = MixtralDecodeModel(MIXTRAL_8X7B, max_batch=max(batches),
+                               max_seq=1024, moe_impl="grouped")
+    rows = []
+    for b in batches:
+        base_impl = "dense" if b <= 64 else "sparse"
+        model.moe_impl = "grouped"
+        grouped = measure_itl(model, b, 512, iters=iters, use_graph=True)
+        model.moe_impl = base_impl
+        base = measure_itl(model, b, 512, iters=iters,
+                           use_graph=base_impl == "dense")
+        rows.append((b, base_impl, base, grouped))
+        print(f"b={b:3d} {base_impl:6s} {base:8.3f} ms  grouped "
+              f"{grouped:8.3f} ms  x{base / grouped:.2f}", flush=True)
+    itls = [r[3] for r in rows]
+    alpha, beta, r2 = fit_itl_curve(batches, itls)
+    rec = {
+        "model": MIXTRAL_8X7B.name,
+        "moe_impl": "grouped",
+        "graph": True,
+        "context_len": 512,
+        "gpu_count": 1,
+        "alpha_ms": alpha,
+        "beta_ms": beta,
+        "r_squared": r2,
+        "batch_sizes": batches,
+        "itl_ms": itls,
+        "baseline_impl": [r[1] for r in rows],
+        "baseline_graph": [r[1] == "dense" for r in rows],
+        "baseline_itl_ms": [r[2] for r in rows],
+        "weights_gib": MIXTRAL_8X7B.weight_bytes() / 2**30,
+        "decode_tokens_per_s_peak": max(
+            b / (t / 1000.0) for b, t in zip(batches, itls)
+        ),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "calibration_mixtral_grouped.json"),
+              "w") as f:
+        json.dump(rec, f, indent=2)
+    with open(os.path.join(out_dir, "moe_grouped_ab.txt"), "w") as f:
+        f.write("Mixtral-8x7B decode ITL, ctx 512, one MI355X, median of "
+                f"{iters} steps\n")
+        f.write("grouped: hipGraph replay; dense: hipGraph replay; "
+                "sparse: eager (not capturable)\n\n")
+        f.write(f"{'batch':>5} {'baseline':>8} {'base ms':>9} "
+                f"{'grouped ms':>10} {'speedup':>8}\n")
+        for b, impl, base, grouped in rows:
+            f.write(f"{b:5d} {impl:>8} {base:9.3f} {grouped:10.3f} "
+                    f"{base / grouped:7.2f}x\n")
+        f.write(f"\ngrouped fit: alpha={alpha:.3f} ms beta={beta:.4f} "
+                f"ms/seq r2={r2:.3f}\n")
 
 
 def graph_ab():
@@ -311,3 +393,7 @@ def moe_bench():
     w = torch.softmax(w, dim=-1).to(dt)
     bench("full _moe_mlp_dense", lambda: m._moe_mlp_dense(layer, h2, w, sel))
     bench("full _moe_mlp_sparse", lambda: m._moe_mlp_sparse(layer, h2, w, sel), n=3)
+
+
+if __name__ == "__main__":
+    main()

@@ -12,7 +12,9 @@ rope_append_kv, GQA decode attention) + top-2 routed expert MLPs. At
 decode batches the expert MLPs run DENSE-batched — one hipBLASLt
 strided-batched GEMM pair per layer over all experts (see _moe_mlp) —
 because decode MoE is weight-streaming-bound and the sparse gather path's
-per-expert `nonzero()` syncs dominate.
+per-expert `nonzero()` syncs dominate. `moe_impl="grouped"` instead routes
+on the device and multiplies only the routed (token, expert) pairs
+(ops.moe_mlp, csrc/moe.hip): what a serving engine's fused MoE does.
 """
 from __future__ import annotations
 
@@ -132,6 +134,15 @@ class _MoELayer:
         self.w_down_t = down_stacked.transpose(1, 2).contiguous()
 
 
+# expert-MLP implementations selectable per engine:
+#   auto    — dense for decode B ≤ 64, sparse above and for prefill
+#   dense   — every expert on every token (one GEMM pair per layer)
+#   sparse  — per-expert gather with a host sync per expert
+#   grouped — device-side routing + grouped MFMA GEMMs (ops.moe_mlp):
+#             only routed experts stream, no host sync, graph-capturable
+MOE_IMPLS = ("auto", "dense", "sparse", "grouped")
+
+
 class MixtralDecodeModel:
     """Decode-only MoE engine; same KV-cache layout as LlamaDecodeModel."""
 
@@ -143,8 +154,14 @@ class MixtralDecodeModel:
         device: str = "cuda",
         seed: int = 0,
         kv_dtype: str = "bf16",
+        moe_impl: str = "auto",
     ):
+        if moe_impl not in MOE_IMPLS:
+            raise ValueError(
+                f"moe_impl must be one of {MOE_IMPLS}, got {moe_impl!r}"
+            )
         self.cfg = cfg
+        self.moe_impl = moe_impl
         self.device = torch.device(device)
         self.dtype = torch.bfloat16
         self.kv_dtype = kv_dtype
@@ -216,13 +233,24 @@ class MixtralDecodeModel:
         sparse gather path (compute starts to matter), which is also the
         numerics reference for the GPU tests.
         """
+        return self._moe_mlp_impl(layer, h2, dense=h2.shape[0] <= 64)
+
+    def _moe_mlp_impl(self, layer: _MoELayer, h2, dense: bool):
+        """Route and run the expert MLP; `dense` is what moe_impl="auto"
+        picks for this call (decode B ≤ 64), the forced impls ignore it."""
         cfg = self.cfg
-        B = h2.shape[0]
         router_logits = (h2.float() @ layer.w_router.t().float())  # [B, E]
+        if self.moe_impl == "grouped":
+            return ops.moe_mlp(
+                h2, router_logits, layer.w_gate_up_stacked,
+                layer.w_down_stacked, cfg.top_k,
+            )
         weights, selected = torch.topk(router_logits, cfg.top_k, dim=-1)
         weights = torch.softmax(weights, dim=-1).to(h2.dtype)  # [B, K]
 
-        if B <= 64:
+        if self.moe_impl != "auto":
+            dense = self.moe_impl == "dense"
+        if dense:
             return self._moe_mlp_dense(layer, h2, weights, selected)
         return self._moe_mlp_sparse(layer, h2, weights, selected)
 
@@ -305,7 +333,8 @@ class MixtralDecodeModel:
         compute-bound (each expert sees ~T·k/E of T = B·S tokens, and
         T is large), so dense-batching would genuinely 4× the MLP FLOPs —
         the opposite trade from decode (see _moe_mlp). The per-expert
-        `nonzero()` syncs amortize over one large pass.
+        `nonzero()` syncs amortize over one large pass. A forced
+        `moe_impl` (dense / sparse / grouped) applies here too.
         """
         cfg = self.cfg
         B, S = token_ids.shape
@@ -378,10 +407,7 @@ class MixtralDecodeModel:
             x = attn @ layer.wo.t()
 
             h2 = ops.rmsnorm(x, layer.post_attn_norm, residual, cfg.rms_eps)
-            router_logits = h2.float() @ layer.w_router.t().float()
-            weights, selected = torch.topk(router_logits, cfg.top_k, dim=-1)
-            weights = torch.softmax(weights, dim=-1).to(h2.dtype)
-            x = self._moe_mlp_sparse(layer, h2, weights, selected)
+            x = self._moe_mlp_impl(layer, h2, dense=False)
 
         final = ops.rmsnorm(x, self.final_norm, residual, cfg.rms_eps)
         last = final.reshape(B, S, cfg.hidden_size)[:, -1].contiguous()

@@ -132,6 +132,96 @@ def gqa_decode_attn_ref(
     return out
 
 
+def moe_route_ref(router_logits: torch.Tensor, top_k: int):
+    """MoE routing reference.
+
+    Returns (topk_idx [T,K] int32 in descending logit order — lowest
+    expert index wins an exact tie, topk_w [T,K] fp32 softmax over the K
+    selected logits, expert_offsets [E+1] int32 exclusive prefix of
+    per-expert slot counts, sorted_slots [T*K] int32 slot ids t*K+k
+    grouped by expert and ascending within an expert)."""
+    logits = router_logits.float()
+    E = logits.shape[1]
+    # a stable descending sort keeps the lower index first among equals
+    vals, idx = torch.sort(logits, dim=-1, descending=True, stable=True)
+    vals, idx = vals[:, :top_k], idx[:, :top_k]
+    topk_w = torch.softmax(vals, dim=-1)
+    flat = idx.reshape(-1)
+    sorted_slots = torch.sort(flat, stable=True).indices
+    counts = torch.bincount(flat, minlength=E)
+    offsets = torch.zeros(E + 1, dtype=torch.int64, device=logits.device)
+    offsets[1:] = torch.cumsum(counts, dim=0)
+    return (
+        idx.to(torch.int32).contiguous(),
+        topk_w.contiguous(),
+        offsets.to(torch.int32),
+        sorted_slots.to(torch.int32),
+    )
+
+
+def moe_gate_up_swiglu_ref(
+    x: torch.Tensor,
+    w_gate_up: torch.Tensor,
+    expert_offsets: torch.Tensor,
+    sorted_slots: torch.Tensor,
+    top_k: int,
+) -> torch.Tensor:
+    """fp32 [T*K, I]: silu(g)*u of x[slot // K] @ w_gate_up[e].T for the
+    expert e owning each sorted position; w_gate_up is [E, 2I, H]."""
+    E, two_i, _ = w_gate_up.shape
+    inter = two_i // 2
+    offs = expert_offsets.tolist()
+    tokens = torch.div(sorted_slots.long(), top_k, rounding_mode="floor")
+    out = torch.zeros(
+        sorted_slots.numel(), inter, dtype=torch.float32, device=x.device
+    )
+    for e in range(E):
+        lo, hi = offs[e], offs[e + 1]
+        if hi == lo:
+            continue
+        gu = x[tokens[lo:hi]].float() @ w_gate_up[e].float().t()
+        out[lo:hi] = torch.nn.functional.silu(gu[:, :inter]) * gu[:, inter:]
+    return out
+
+
+def moe_down_combine_ref(
+    act_sorted: torch.Tensor,
+    w_down: torch.Tensor,
+    topk_w: torch.Tensor,
+    expert_offsets: torch.Tensor,
+    sorted_slots: torch.Tensor,
+) -> torch.Tensor:
+    """fp32 [T, H]: sum_k topk_w[t,k] * (act_sorted[pos(t,k)] @
+    w_down[e].T); w_down is [E, H, I]."""
+    E, hidden, _ = w_down.shape
+    T, K = topk_w.shape
+    offs = expert_offsets.tolist()
+    y = torch.zeros(T * K, hidden, dtype=torch.float32, device=w_down.device)
+    slots = sorted_slots.long()
+    for e in range(E):
+        lo, hi = offs[e], offs[e + 1]
+        if hi == lo:
+            continue
+        y[slots[lo:hi]] = act_sorted[lo:hi].float() @ w_down[e].float().t()
+    return (y.reshape(T, K, hidden) * topk_w.float().unsqueeze(-1)).sum(dim=1)
+
+
+def moe_mlp_ref(
+    x: torch.Tensor,
+    router_logits: torch.Tensor,
+    w_gate_up: torch.Tensor,
+    w_down: torch.Tensor,
+    top_k: int,
+) -> torch.Tensor:
+    """fp32 routed expert MLP; `act` is rounded to bf16 between the two
+    GEMMs exactly as the kernels do."""
+    _, topk_w, offsets, slots = moe_route_ref(router_logits, top_k)
+    act = moe_gate_up_swiglu_ref(x, w_gate_up, offsets, slots, top_k)
+    return moe_down_combine_ref(
+        act.to(torch.bfloat16), w_down, topk_w, offsets, slots
+    )
+
+
 # --- dispatching public ops (GPU → HIP kernel, CPU → reference) ---
 
 
@@ -228,6 +318,85 @@ def gqa_decode_attn(
     return gqa_decode_attn_ref(q, k_cache, v_cache, context_lens, scale).to(
         q.dtype
     )
+
+
+def moe_route(router_logits: torch.Tensor, top_k: int):
+    """Device-side MoE routing from fp32 router logits [T, E]; see
+    moe_route_ref for the four outputs. Nothing is read back to the host,
+    so the op is graph-capturable."""
+    if router_logits.is_cuda:
+        return tuple(
+            _require_ext().moe_route(
+                router_logits.float().contiguous(), top_k
+            )
+        )
+    return moe_route_ref(router_logits, top_k)
+
+
+def moe_gate_up_swiglu(
+    x: torch.Tensor,
+    w_gate_up: torch.Tensor,
+    expert_offsets: torch.Tensor,
+    sorted_slots: torch.Tensor,
+    top_k: int,
+) -> torch.Tensor:
+    """Grouped gate_up GEMM + SwiGLU over the routed rows only: bf16
+    [T*K, I] in expert-sorted order, against the stacked [E, 2I, H]."""
+    if x.is_cuda:
+        return _require_ext().moe_gate_up_swiglu(
+            x, w_gate_up, expert_offsets, sorted_slots, top_k
+        )
+    return moe_gate_up_swiglu_ref(
+        x, w_gate_up, expert_offsets, sorted_slots, top_k
+    ).to(x.dtype)
+
+
+def moe_down_combine(
+    act_sorted: torch.Tensor,
+    w_down: torch.Tensor,
+    topk_w: torch.Tensor,
+    expert_offsets: torch.Tensor,
+    sorted_slots: torch.Tensor,
+) -> torch.Tensor:
+    """Grouped down GEMM against the stacked [E, H, I] + top-k combine:
+    bf16 [T, H], summed in a fixed order (deterministic)."""
+    if act_sorted.is_cuda:
+        return _require_ext().moe_down_combine(
+            act_sorted, w_down, topk_w, expert_offsets, sorted_slots
+        )
+    return moe_down_combine_ref(
+        act_sorted, w_down, topk_w, expert_offsets, sorted_slots
+    ).to(act_sorted.dtype)
+
+
+def moe_down_num_splits(
+    tokens: int, top_k: int, num_experts: int, hidden: int, inter: int
+) -> int:
+    """Split-K factor the down GEMM kernel picks for these static shapes."""
+    return int(
+        _require_ext().moe_down_splits(
+            tokens, top_k, num_experts, hidden, inter
+        )
+    )
+
+
+def moe_mlp(
+    x: torch.Tensor,
+    router_logits: torch.Tensor,
+    w_gate_up: torch.Tensor,
+    w_down: torch.Tensor,
+    top_k: int,
+) -> torch.Tensor:
+    """Routed expert MLP: x [T, H] bf16, router_logits [T, E] fp32,
+    stacked expert weights [E, 2I, H] / [E, H, I] → bf16 [T, H].
+
+    Only routed experts' weights are streamed and only routed tokens are
+    multiplied; no step syncs with the host (csrc/moe.hip)."""
+    if x.is_cuda:
+        _, topk_w, offsets, slots = moe_route(router_logits, top_k)
+        act = moe_gate_up_swiglu(x, w_gate_up, offsets, slots, top_k)
+        return moe_down_combine(act, w_down, topk_w, offsets, slots)
+    return moe_mlp_ref(x, router_logits, w_gate_up, w_down, top_k).to(x.dtype)
 
 
 def enable_tuned_gemms() -> bool:

@@ -89,6 +89,26 @@ extern "C" void launch_gqa_decode_attn_v4(void* out, void* workspace,
                                           int max_seq, int num_splits,
                                           float scale, hipStream_t stream);
 
+extern "C" int moe_num_m_tiles(int TK, int E);
+extern "C" int moe_down_num_splits(int TK, int E, int H, int I);
+extern "C" void launch_moe_route(int* topk_idx, float* topk_w,
+                                 int* expert_offsets, int* sorted_slots,
+                                 const float* logits, int T, int E, int K,
+                                 hipStream_t stream);
+extern "C" void launch_moe_gate_up_swiglu(void* act, const void* x,
+                                          const void* w,
+                                          const int* expert_offsets,
+                                          const int* sorted_slots, int T,
+                                          int E, int top_k, int H, int I,
+                                          hipStream_t stream);
+extern "C" void launch_moe_down_combine(void* out, float* ws,
+                                        const void* act, const void* w,
+                                        const float* topk_w,
+                                        const int* expert_offsets,
+                                        const int* sorted_slots, int T,
+                                        int E, int top_k, int H, int I,
+                                        int num_splits, hipStream_t stream);
+
 namespace {
 
 hipStream_t current_stream() {
@@ -382,6 +402,130 @@ torch::Tensor prefill_attn(torch::Tensor q, torch::Tensor k_cache,
   return out;
 }
 
+// --- routed MoE expert MLP (csrc/moe.hip) ---
+
+void check_i32_contig(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == torch::kInt32, name, " must be int32");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+}
+
+// The m-tile grid dimension is launched at its static bound; keep it (and
+// every int index the kernels form) comfortably in range.
+void check_moe_sizes(long T, long E, long K) {
+  TORCH_CHECK(T >= 1, "need at least one token");
+  TORCH_CHECK(E >= 1 && E <= 64, "num_experts must be in [1, 64]");
+  TORCH_CHECK(K >= 1 && K <= 8 && K <= E, "top_k must be in [1, min(8, E)]");
+  TORCH_CHECK(T * K < (1L << 30), "T * top_k too large");
+  TORCH_CHECK(moe_num_m_tiles((int)(T * K), (int)E) <= 65535,
+              "too many m-tiles for one launch");
+}
+
+// router_logits fp32 [T, E] → (topk_idx [T,K] i32, topk_w [T,K] f32,
+// expert_offsets [E+1] i32, sorted_slots [T*K] i32), all on device.
+std::vector<torch::Tensor> moe_route(torch::Tensor router_logits,
+                                     int64_t top_k) {
+  TORCH_CHECK(router_logits.is_cuda(), "router_logits must be on GPU");
+  TORCH_CHECK(router_logits.scalar_type() == torch::kFloat,
+              "router_logits must be float32");
+  TORCH_CHECK(router_logits.is_contiguous(),
+              "router_logits must be contiguous");
+  TORCH_CHECK(router_logits.dim() == 2, "router_logits must be [T, E]");
+  const long T = router_logits.size(0);
+  const long E = router_logits.size(1);
+  check_moe_sizes(T, E, top_k);
+  auto i32 = router_logits.options().dtype(torch::kInt32);
+  auto topk_idx = torch::empty({T, top_k}, i32);
+  auto topk_w = torch::empty({T, top_k}, router_logits.options());
+  auto expert_offsets = torch::empty({E + 1}, i32);
+  auto sorted_slots = torch::empty({T * top_k}, i32);
+  launch_moe_route(topk_idx.data_ptr<int>(), topk_w.data_ptr<float>(),
+                   expert_offsets.data_ptr<int>(),
+                   sorted_slots.data_ptr<int>(),
+                   router_logits.data_ptr<float>(), (int)T, (int)E,
+                   (int)top_k, current_stream());
+  return {topk_idx, topk_w, expert_offsets, sorted_slots};
+}
+
+// act_sorted [T*K, I] = silu(g)·u of x[token] · w_gate_up[e]^T, rows in
+// expert-sorted order. w_gate_up is the stacked [E, 2I, H] tensor.
+torch::Tensor moe_gate_up_swiglu(torch::Tensor x, torch::Tensor w_gate_up,
+                                 torch::Tensor expert_offsets,
+                                 torch::Tensor sorted_slots, int64_t top_k) {
+  check_bf16_contig(x, "x");
+  check_bf16_contig(w_gate_up, "w_gate_up");
+  check_i32_contig(expert_offsets, "expert_offsets");
+  check_i32_contig(sorted_slots, "sorted_slots");
+  TORCH_CHECK(x.dim() == 2 && w_gate_up.dim() == 3,
+              "x [T,H], w_gate_up [E,2I,H]");
+  const long T = x.size(0);
+  const long H = x.size(1);
+  const long E = w_gate_up.size(0);
+  check_moe_sizes(T, E, top_k);
+  TORCH_CHECK(w_gate_up.size(2) == H, "H mismatch");
+  TORCH_CHECK(w_gate_up.size(1) % 2 == 0, "w_gate_up rows must be 2*I");
+  const long I = w_gate_up.size(1) / 2;
+  TORCH_CHECK(H % 128 == 0, "H (K-dim) must be a multiple of 128");
+  TORCH_CHECK(I % 16 == 0, "I (N-dim) must be a multiple of 16");
+  TORCH_CHECK(expert_offsets.numel() == E + 1, "expert_offsets must be [E+1]");
+  TORCH_CHECK(sorted_slots.numel() == T * top_k,
+              "sorted_slots must be [T*top_k]");
+  auto act = torch::empty({T * top_k, I}, x.options());
+  launch_moe_gate_up_swiglu(act.data_ptr(), x.data_ptr(),
+                            w_gate_up.data_ptr(),
+                            expert_offsets.data_ptr<int>(),
+                            sorted_slots.data_ptr<int>(), (int)T, (int)E,
+                            (int)top_k, (int)H, (int)I, current_stream());
+  return act;
+}
+
+// out [T, H] = Σ_k topk_w[t,k] · (act_sorted[pos(t,k)] · w_down[e]^T),
+// w_down the stacked [E, H, I] tensor; split-K partials go through an
+// fp32 workspace indexed by slot and are summed in a fixed order.
+torch::Tensor moe_down_combine(torch::Tensor act_sorted, torch::Tensor w_down,
+                               torch::Tensor topk_w,
+                               torch::Tensor expert_offsets,
+                               torch::Tensor sorted_slots) {
+  check_bf16_contig(act_sorted, "act_sorted");
+  check_bf16_contig(w_down, "w_down");
+  check_i32_contig(expert_offsets, "expert_offsets");
+  check_i32_contig(sorted_slots, "sorted_slots");
+  TORCH_CHECK(topk_w.is_cuda() && topk_w.scalar_type() == torch::kFloat &&
+                  topk_w.is_contiguous() && topk_w.dim() == 2,
+              "topk_w must be contiguous float32 [T, K] on GPU");
+  TORCH_CHECK(act_sorted.dim() == 2 && w_down.dim() == 3,
+              "act_sorted [T*K,I], w_down [E,H,I]");
+  const long T = topk_w.size(0);
+  const long K = topk_w.size(1);
+  const long E = w_down.size(0);
+  const long H = w_down.size(1);
+  const long I = w_down.size(2);
+  check_moe_sizes(T, E, K);
+  TORCH_CHECK(act_sorted.size(0) == T * K && act_sorted.size(1) == I,
+              "act_sorted shape mismatch");
+  TORCH_CHECK(I % 128 == 0, "I (K-dim) must be a multiple of 128");
+  TORCH_CHECK(H % 16 == 0, "H (N-dim) must be a multiple of 16");
+  TORCH_CHECK(expert_offsets.numel() == E + 1, "expert_offsets must be [E+1]");
+  TORCH_CHECK(sorted_slots.numel() == T * K, "sorted_slots must be [T*K]");
+  const int sk = moe_down_num_splits((int)(T * K), (int)E, (int)H, (int)I);
+  auto ws = torch::empty({(long)sk * T * K * H},
+                         act_sorted.options().dtype(torch::kFloat32));
+  auto out = torch::empty({T, H}, act_sorted.options());
+  launch_moe_down_combine(out.data_ptr(), ws.data_ptr<float>(),
+                          act_sorted.data_ptr(), w_down.data_ptr(),
+                          topk_w.data_ptr<float>(),
+                          expert_offsets.data_ptr<int>(),
+                          sorted_slots.data_ptr<int>(), (int)T, (int)E,
+                          (int)K, (int)H, (int)I, sk, current_stream());
+  return out;
+}
+
+int64_t moe_down_splits(int64_t tokens, int64_t top_k, int64_t num_experts,
+                        int64_t hidden, int64_t inter) {
+  return moe_down_num_splits((int)(tokens * top_k), (int)num_experts,
+                             (int)hidden, (int)inter);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -423,6 +567,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "GQA decode attention, MFMA scores + MFMA PV variant",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("context_lens"), py::arg("scale"));
+  m.def("moe_route", &moe_route,
+        "MoE routing: top-k, softmax weights, expert offsets, sorted slots",
+        py::arg("router_logits"), py::arg("top_k"));
+  m.def("moe_gate_up_swiglu", &moe_gate_up_swiglu,
+        "Grouped gate_up GEMM + SwiGLU over expert-sorted rows",
+        py::arg("x"), py::arg("w_gate_up"), py::arg("expert_offsets"),
+        py::arg("sorted_slots"), py::arg("top_k"));
+  m.def("moe_down_combine", &moe_down_combine,
+        "Grouped down GEMM + deterministic top-k combine",
+        py::arg("act_sorted"), py::arg("w_down"), py::arg("topk_w"),
+        py::arg("expert_offsets"), py::arg("sorted_slots"));
+  m.def("moe_down_splits", &moe_down_splits,
+        "Split-K factor moe_down_combine uses for these static shapes",
+        py::arg("tokens"), py::arg("top_k"), py::arg("num_experts"),
+        py::arg("hidden"), py::arg("inter"));
   m.def("gqa_decode_attn_v3", &gqa_decode_attn_v3,
         "GQA decode attention, pre-MFMA shared-tile variant",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
