@@ -84,17 +84,24 @@ def attn_bench():
         ext = _require_ext()
         scale = 128 ** -0.5
         import time as _t
-        for name, fn in [("v3", ext.gqa_decode_attn_v3),
-                         ("v4", ext.gqa_decode_attn_v4),
-                         ("v5", ext.gqa_decode_attn_v5)]:
-            for _ in range(3):
-                fn(q, k, v, lens, scale)
+        for name in ("auto", "v4", "v5"):
+            def fn(variant=name):
+                return ext.gqa_decode_attn(q, k, v, lens, scale,
+                                           variant=variant)
+
+            for _ in range(50):
+                fn()
             torch.cuda.synchronize()
-            n = 20
+            # calls are tens of µs: time a window of >= 0.25 s, not the clock
+            n = 0
             t0 = _t.perf_counter()
-            for _ in range(n):
-                fn(q, k, v, lens, scale)
-            torch.cuda.synchronize()
+            while True:
+                for _ in range(500):
+                    fn()
+                n += 500
+                torch.cuda.synchronize()
+                if _t.perf_counter() - t0 >= 0.25:
+                    break
             us = (_t.perf_counter() - t0) / n * 1e6
             kv_bytes = 2 * batch * ctx * hk * 128 * 2
             print(f"attn[{name}] b={batch} hq={hq} hk={hk} ctx={ctx}: "

@@ -291,7 +291,7 @@ class TestAttnV4:
                              dtype=torch.int32)
         lens[0] = ctx
         scale = 128 ** -0.5
-        out = ext.gqa_decode_attn_v4(q, k, v, lens, scale)
+        out = ext.gqa_decode_attn(q, k, v, lens, scale, variant="v4")
         ref = gqa_decode_attn_ref(
             q.float().cpu(), k.float().cpu(), v.float().cpu(),
             lens.cpu(), scale,
@@ -299,18 +299,37 @@ class TestAttnV4:
         torch.testing.assert_close(out.float().cpu(), ref, atol=2e-2,
                                    rtol=2e-2)
 
-    def test_v4_matches_v3(self, dev):
+    def test_auto_dispatch_matches_forced(self, dev):
+        """Pins the dispatch rule (v5 when G >= 8 or unsplit, else v4):
+        `auto` must be exactly the kernel the rule names, so the outputs
+        are bit-equal on the same inputs."""
         from wva_amd.ops import _require_ext
 
         ext = _require_ext()
         torch.manual_seed(5)
-        q = torch.randn(8, 32, 128, device=dev, dtype=torch.bfloat16)
-        k = torch.randn(8, 8, 640, 128, device=dev, dtype=torch.bfloat16)
-        v = torch.randn(8, 8, 640, 128, device=dev, dtype=torch.bfloat16)
-        lens = torch.full((8,), 640, device=dev, dtype=torch.int32)
-        a = ext.gqa_decode_attn(q, k, v, lens, 128 ** -0.5)
-        b = ext.gqa_decode_attn_v4(q, k, v, lens, 128 ** -0.5)
-        torch.testing.assert_close(a.float(), b.float(), atol=5e-3, rtol=5e-3)
+        # (8, 32, 8, 640): G = 4, 5 splits -> v4;  (2, 64, 8, 300): G = 8 -> v5
+        for (batch, hq, hk, ctx), picked in [((8, 32, 8, 640), "v4"),
+                                             ((2, 64, 8, 300), "v5")]:
+            q = torch.randn(batch, hq, 128, device=dev, dtype=torch.bfloat16)
+            k = torch.randn(batch, hk, ctx, 128, device=dev,
+                            dtype=torch.bfloat16)
+            v = torch.randn(batch, hk, ctx, 128, device=dev,
+                            dtype=torch.bfloat16)
+            lens = torch.full((batch,), ctx, device=dev, dtype=torch.int32)
+            a = ext.gqa_decode_attn(q, k, v, lens, 128 ** -0.5)
+            b = ext.gqa_decode_attn(q, k, v, lens, 128 ** -0.5,
+                                    variant=picked)
+            assert torch.equal(a, b), (batch, hq, hk, ctx, picked)
+
+    def test_unknown_variant_rejected(self, dev):
+        from wva_amd.ops import _require_ext
+
+        ext = _require_ext()
+        q = torch.zeros(1, 8, 128, device=dev, dtype=torch.bfloat16)
+        kv = torch.zeros(1, 2, 64, 128, device=dev, dtype=torch.bfloat16)
+        lens = torch.ones(1, device=dev, dtype=torch.int32)
+        with pytest.raises(RuntimeError, match="variant"):
+            ext.gqa_decode_attn(q, kv, kv, lens, 1.0, variant="v3")
 
 
 class TestSkinnyLinear:
@@ -363,7 +382,7 @@ class TestAttnV5:
                              dtype=torch.int32)
         lens[0] = ctx
         scale = 128 ** -0.5
-        out = ext.gqa_decode_attn_v5(q, k, v, lens, scale)
+        out = ext.gqa_decode_attn(q, k, v, lens, scale, variant="v5")
         ref = gqa_decode_attn_ref(
             q.float().cpu(), k.float().cpu(), v.float().cpu(),
             lens.cpu(), scale,
@@ -505,14 +524,16 @@ class TestFp8KvGpu:
                 torch.float8_e4m3fn)
             lens = torch.full((B,), ctx, device=dev, dtype=torch.int32)
             scale = 128 ** -0.5
-            out = ext.gqa_decode_attn(q, k8, v8, lens, scale)
             ref = gqa_decode_attn_ref(
                 q.float().cpu(), k8.float().cpu(), v8.float().cpu(),
                 lens.cpu(), scale,
             )
-            torch.testing.assert_close(
-                out.float().cpu(), ref, atol=3e-2, rtol=3e-2
-            )
+            for variant in ("auto", "v4", "v5"):
+                out = ext.gqa_decode_attn(q, k8, v8, lens, scale,
+                                          variant=variant)
+                torch.testing.assert_close(
+                    out.float().cpu(), ref, atol=3e-2, rtol=3e-2
+                )
 
     def test_fp8_rope_append(self, dev):
         from wva_amd import ops

@@ -15,6 +15,19 @@ using bf16x2 = __hip_bfloat162;
 __device__ __forceinline__ float bf2f(bf16 v) { return __bfloat162float(v); }
 __device__ __forceinline__ bf16 f2bf(float v) { return __float2bfloat16(v); }
 
+// MFMA 16x16x32 operand fragments: 8 bf16 (raw bits) of A or B per lane,
+// 4 fp32 of C/D per lane.
+typedef __attribute__((ext_vector_type(8))) short bf16x8_frag;
+typedef __attribute__((ext_vector_type(4))) float f32x4_frag;
+using moe_bf16x8 = bf16x8_frag;  // names moe.hip uses
+using moe_f32x4 = f32x4_frag;
+
+// fp32 -> bf16 raw bits (round-to-nearest-even via hardware convert)
+__device__ __forceinline__ short f2bf_bits(float v) {
+  const bf16 b = f2bf(v);
+  return *reinterpret_cast<const short*>(&b);
+}
+
 // Full wave64 reduction (sum). 6 xor-shuffle steps across 64 lanes.
 __device__ __forceinline__ float wave_reduce_sum(float v) {
 #pragma unroll

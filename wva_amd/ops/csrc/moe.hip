@@ -34,9 +34,6 @@
 #define MOE_MAX_E 64
 #define MOE_MAX_K 8
 
-typedef __attribute__((ext_vector_type(8))) short moe_bf16x8;
-typedef __attribute__((ext_vector_type(4))) float moe_f32x4;
-
 // ---------------------------------------------------------------- route
 
 // One thread per token: top-k by repeated argmax (strict '>' so the lowest

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <c10/hip/HIPStream.h>
 
+#include <string>
+
 extern "C" void launch_rmsnorm(void* out, void* residual_out,
                                const void* input, const void* residual,
                                const void* weight, float eps, int rows,
@@ -25,24 +27,6 @@ extern "C" void launch_rope_append_kv_fp8(const void* qkv, void* q_out,
                                           int num_q_heads, int num_kv_heads,
                                           int head_dim, int max_seq,
                                           float theta, hipStream_t stream);
-extern "C" void launch_gqa_decode_attn_v4_ex(void* out, void* workspace,
-                                             const void* q,
-                                             const void* k_cache,
-                                             const void* v_cache,
-                                             const int* context_lens,
-                                             int batch, int num_q_heads,
-                                             int num_kv_heads, int max_seq,
-                                             int num_splits, float scale,
-                                             int kv_fp8, hipStream_t stream);
-extern "C" void launch_gqa_decode_attn_v5_ex(void* out, void* workspace,
-                                             const void* q,
-                                             const void* k_cache,
-                                             const void* v_cache,
-                                             const int* context_lens,
-                                             int batch, int num_q_heads,
-                                             int num_kv_heads, int max_seq,
-                                             int num_splits, float scale,
-                                             int kv_fp8, hipStream_t stream);
 extern "C" void launch_rope_append_kv(const void* qkv, void* q_out,
                                       void* k_cache, void* v_cache,
                                       const int* positions, int batch,
@@ -73,21 +57,8 @@ extern "C" void launch_gqa_decode_attn(void* out, void* workspace,
                                        const int* context_lens, int batch,
                                        int num_q_heads, int num_kv_heads,
                                        int max_seq, int num_splits,
-                                       float scale, hipStream_t stream);
-extern "C" void launch_gqa_decode_attn_v5(void* out, void* workspace,
-                                          const void* q, const void* k_cache,
-                                          const void* v_cache,
-                                          const int* context_lens, int batch,
-                                          int num_q_heads, int num_kv_heads,
-                                          int max_seq, int num_splits,
-                                          float scale, hipStream_t stream);
-extern "C" void launch_gqa_decode_attn_v4(void* out, void* workspace,
-                                          const void* q, const void* k_cache,
-                                          const void* v_cache,
-                                          const int* context_lens, int batch,
-                                          int num_q_heads, int num_kv_heads,
-                                          int max_seq, int num_splits,
-                                          float scale, hipStream_t stream);
+                                       float scale, int variant, int kv_fp8,
+                                       hipStream_t stream);
 
 extern "C" int moe_num_m_tiles(int TK, int E);
 extern "C" int moe_down_num_splits(int TK, int E, int H, int I);
@@ -227,16 +198,32 @@ torch::Tensor silu_mul_fused(torch::Tensor gate_up) {
   return out;
 }
 
-torch::Tensor gqa_decode_attn_impl(torch::Tensor q, torch::Tensor k_cache,
-                                   torch::Tensor v_cache,
-                                   torch::Tensor context_lens, double scale,
-                                   int use_v4) {
+// Decode attention kernel choice. Auto is the measured per-shape-class
+// dispatch (profiles/attn_v4_ab.txt): v5 (MFMA scores + MFMA PV) wins
+// when the PV matrix is well-utilized (G = 8) or the grid is unsplit
+// (large batch); v4 (MFMA scores, vector PV) wins for G < 8 with split-KV
+// where v5's padded 16-row PV and its third per-tile barrier cost more
+// than the VALU sweep it replaces. V4/V5 pin a kernel on any shape, for
+// tests and the microbench.
+enum class AttnVariant { Auto, V4, V5 };
+
+AttnVariant parse_attn_variant(const std::string& name) {
+  TORCH_CHECK(name == "auto" || name == "v4" || name == "v5",
+              "variant must be \"auto\", \"v4\" or \"v5\", got \"", name, "\"");
+  return name == "v4"   ? AttnVariant::V4
+         : name == "v5" ? AttnVariant::V5
+                        : AttnVariant::Auto;
+}
+
+torch::Tensor gqa_decode_attn(torch::Tensor q, torch::Tensor k_cache,
+                              torch::Tensor v_cache,
+                              torch::Tensor context_lens, double scale,
+                              const std::string& variant_name) {
+  AttnVariant variant = parse_attn_variant(variant_name);
   check_bf16_contig(q, "q");
   const bool kv_fp8 = check_cache_contig(k_cache, "k_cache");
   TORCH_CHECK(check_cache_contig(v_cache, "v_cache") == kv_fp8,
               "k/v cache dtype mismatch");
-  TORCH_CHECK(!(kv_fp8 && use_v4 == 0),
-              "fp8 KV cache requires the v4/v5 MFMA kernels");
   TORCH_CHECK(context_lens.is_cuda() &&
                   context_lens.scalar_type() == torch::kInt32,
               "context_lens must be int32 on GPU");
@@ -250,67 +237,30 @@ torch::Tensor gqa_decode_attn_impl(torch::Tensor q, torch::Tensor k_cache,
   const int max_seq = k_cache.size(2);
   TORCH_CHECK(head_dim == 128, "head_dim must be 128 (Llama-3 family)");
   TORCH_CHECK(num_q_heads % num_kv_heads == 0, "Hq must divide by Hk");
-  TORCH_CHECK(num_q_heads / num_kv_heads <= 8, "GQA group size must be <= 8");
+  const int G = num_q_heads / num_kv_heads;
+  TORCH_CHECK(G <= 8, "GQA group size must be <= 8");
   TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), "k/v cache mismatch");
   auto out = torch::empty_like(q);
   const int num_splits =
       gqa_decode_attn_num_splits(batch, num_kv_heads, max_seq);
+  if (variant == AttnVariant::Auto) {
+    variant = (G >= 8 || num_splits == 1) ? AttnVariant::V5 : AttnVariant::V4;
+  }
   torch::Tensor workspace;
   void* ws_ptr = nullptr;
   if (num_splits > 1) {
-    const int G = num_q_heads / num_kv_heads;
     workspace = torch::empty(
         {(long)batch * num_kv_heads * G * num_splits * (2 + head_dim)},
         q.options().dtype(torch::kFloat32));
     ws_ptr = workspace.data_ptr();
   }
-  if (use_v4 == 0) {
-    launch_gqa_decode_attn(out.data_ptr(), ws_ptr, q.data_ptr(),
-                           k_cache.data_ptr(), v_cache.data_ptr(),
-                           context_lens.data_ptr<int>(), batch, num_q_heads,
-                           num_kv_heads, max_seq, num_splits, (float)scale,
-                           current_stream());
-  } else {
-    auto launch = use_v4 == 2 ? launch_gqa_decode_attn_v5_ex
-                              : launch_gqa_decode_attn_v4_ex;
-    launch(out.data_ptr(), ws_ptr, q.data_ptr(),
-           k_cache.data_ptr(), v_cache.data_ptr(),
-           context_lens.data_ptr<int>(), batch, num_q_heads,
-           num_kv_heads, max_seq, num_splits, (float)scale,
-           kv_fp8 ? 1 : 0, current_stream());
-  }
+  launch_gqa_decode_attn(out.data_ptr(), ws_ptr, q.data_ptr(),
+                         k_cache.data_ptr(), v_cache.data_ptr(),
+                         context_lens.data_ptr<int>(), batch, num_q_heads,
+                         num_kv_heads, max_seq, num_splits, (float)scale,
+                         variant == AttnVariant::V5 ? 5 : 4, kv_fp8 ? 1 : 0,
+                         current_stream());
   return out;
-}
-
-// Default dispatch, measured per shape class (profiles/attn_v4_ab.txt):
-// v5 (MFMA scores + MFMA PV) wins when the PV matrix is well-utilized
-// (G = 8) or the grid is unsplit (large batch); v4 (MFMA scores, vector
-// PV) wins for G < 8 with split-KV where v5's padded 16-row PV and its
-// third per-tile barrier cost more than the VALU sweep it replaces.
-torch::Tensor gqa_decode_attn(torch::Tensor q, torch::Tensor k_cache,
-                              torch::Tensor v_cache,
-                              torch::Tensor context_lens, double scale) {
-  const int G = (int)(q.size(1) / k_cache.size(1));
-  const int splits = gqa_decode_attn_num_splits(
-      (int)q.size(0), (int)k_cache.size(1), (int)k_cache.size(2));
-  const int variant = (G >= 8 || splits == 1) ? 2 : 1;
-  return gqa_decode_attn_impl(q, k_cache, v_cache, context_lens, scale,
-                              variant);
-}
-
-// v5 (MFMA scores + MFMA PV) — A/B variant until measured faster.
-torch::Tensor gqa_decode_attn_v5(torch::Tensor q, torch::Tensor k_cache,
-                                 torch::Tensor v_cache,
-                                 torch::Tensor context_lens, double scale) {
-  return gqa_decode_attn_impl(q, k_cache, v_cache, context_lens, scale,
-                              /*use_v4=*/2);
-}
-
-torch::Tensor gqa_decode_attn_v3(torch::Tensor q, torch::Tensor k_cache,
-                                 torch::Tensor v_cache,
-                                 torch::Tensor context_lens, double scale) {
-  return gqa_decode_attn_impl(q, k_cache, v_cache, context_lens, scale,
-                              /*use_v4=*/0);
 }
 
 // Decode linear: y[M,N] = x[M,K] @ w[N,K]^T on the weight-streaming
@@ -546,13 +496,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("positions"), py::arg("num_q_heads"), py::arg("num_kv_heads"),
         py::arg("theta") = 500000.0);
   m.def("gqa_decode_attn", &gqa_decode_attn,
-        "GQA decode attention over contiguous KV cache",
+        "GQA decode attention over contiguous KV cache; variant pins the "
+        "kernel (\"v4\", \"v5\") instead of the measured dispatch (\"auto\")",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
-        py::arg("context_lens"), py::arg("scale"));
-  m.def("gqa_decode_attn_v4", &gqa_decode_attn,
-        "GQA decode attention, MFMA-scores variant (= default)",
-        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
-        py::arg("context_lens"), py::arg("scale"));
+        py::arg("context_lens"), py::arg("scale"),
+        py::arg("variant") = "auto");
   m.def("prefill_attn", &prefill_attn,
         "Causal flash-attention prefill over head-major KV caches",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
@@ -563,10 +511,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_linear", &skinny_linear,
         "Weight-streaming decode GEMM: x[M,K] @ w[N,K]^T, M <= 64",
         py::arg("x"), py::arg("w"));
-  m.def("gqa_decode_attn_v5", &gqa_decode_attn_v5,
-        "GQA decode attention, MFMA scores + MFMA PV variant",
-        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
-        py::arg("context_lens"), py::arg("scale"));
   m.def("moe_route", &moe_route,
         "MoE routing: top-k, softmax weights, expert offsets, sorted slots",
         py::arg("router_logits"), py::arg("top_k"));
@@ -582,8 +526,4 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Split-K factor moe_down_combine uses for these static shapes",
         py::arg("tokens"), py::arg("top_k"), py::arg("num_experts"),
         py::arg("hidden"), py::arg("inter"));
-  m.def("gqa_decode_attn_v3", &gqa_decode_attn_v3,
-        "GQA decode attention, pre-MFMA shared-tile variant",
-        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
-        py::arg("context_lens"), py::arg("scale"));
 }

@@ -37,14 +37,6 @@
 #define ROW_DW 66          // LDS dword stride for V rows (64 + 2 pad)
 #define P_ROW 66           // LDS stride for P rows (64 positions + pad)
 
-typedef __attribute__((ext_vector_type(8))) short bf16x8_frag;
-typedef __attribute__((ext_vector_type(4))) float f32x4_frag;
-
-__device__ __forceinline__ short pf_f2bf_bits(float v) {
-  const bf16 b = f2bf(v);
-  return *reinterpret_cast<const short*>(&b);
-}
-
 __device__ __forceinline__ float group16_max(float v) {
   // max across the 16-lane group holding one C/D row
 #pragma unroll
@@ -198,8 +190,8 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               const float2_vt f = unpk2_fp8(src[j]);
-              k_frag[2 * j] = pf_f2bf_bits(f[0]);
-              k_frag[2 * j + 1] = pf_f2bf_bits(f[1]);
+              k_frag[2 * j] = f2bf_bits(f[0]);
+              k_frag[2 * j + 1] = f2bf_bits(f[1]);
             }
           } else {
             const short* krow = reinterpret_cast<const short*>(
@@ -288,7 +280,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
           const int p0 = 32 * kk + 8 * (lane / 16);
 #pragma unroll
           for (int i = 0; i < 8; ++i)
-            p_frag[i] = pf_f2bf_bits(p_smem[wave][row][p0 + i]);
+            p_frag[i] = f2bf_bits(p_smem[wave][row][p0 + i]);
         }
 #pragma unroll
         for (int n = 0; n < 8; ++n) {

@@ -32,9 +32,6 @@
 #define NT 64           // W rows per workgroup (16 per wave)
 #define NUM_WAVES 4
 
-typedef __attribute__((ext_vector_type(8))) short bf16x8_frag;
-typedef __attribute__((ext_vector_type(4))) float f32x4_frag;
-
 // NSUB = n-subtiles (16-row groups) per wave: 1 for M <= 16, 2 for
 // larger M — the second subtile reuses the same A fragments, halving
 // the L2 A-read : HBM W-read ratio that bounds the M=64 case.
