@@ -320,6 +320,14 @@ def gqa_decode_attn(
     )
 
 
+def gqa_decode_num_splits(batch: int, num_kv_heads: int, max_seq: int) -> int:
+    """Split-KV factor the decode attention launch picks for a
+    [batch, num_kv_heads, max_seq, 128] cache (1 = unsplit, no merge)."""
+    return int(
+        _require_ext().gqa_decode_attn_splits(batch, num_kv_heads, max_seq)
+    )
+
+
 def moe_route(router_logits: torch.Tensor, top_k: int):
     """Device-side MoE routing from fp32 router logits [T, E]; see
     moe_route_ref for the four outputs. Nothing is read back to the host,

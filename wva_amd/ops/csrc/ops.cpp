@@ -263,6 +263,12 @@ torch::Tensor gqa_decode_attn(torch::Tensor q, torch::Tensor k_cache,
   return out;
 }
 
+int64_t gqa_decode_attn_splits(int64_t batch, int64_t num_kv_heads,
+                               int64_t max_seq) {
+  return gqa_decode_attn_num_splits((int)batch, (int)num_kv_heads,
+                                    (int)max_seq);
+}
+
 // Decode linear: y[M,N] = x[M,K] @ w[N,K]^T on the weight-streaming
 // MFMA kernel (csrc/skinny_gemm.hip). Caller guarantees M <= 64 and
 // K % 128 == 0; larger M belongs to hipBLASLt.
@@ -501,6 +507,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("context_lens"), py::arg("scale"),
         py::arg("variant") = "auto");
+  m.def("gqa_decode_attn_splits", &gqa_decode_attn_splits,
+        "Split-KV factor gqa_decode_attn uses for a [batch, num_kv_heads, "
+        "max_seq, 128] cache",
+        py::arg("batch"), py::arg("num_kv_heads"), py::arg("max_seq"));
   m.def("prefill_attn", &prefill_attn,
         "Causal flash-attention prefill over head-major KV caches",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),

@@ -16,6 +16,10 @@
 
 #include "common.h"
 
+// bf16 destinations: float32 inv_freq and angle, hardware sin/cos (which
+// reduces its argument itself). Measured against a float64 rotation this
+// stays within one bf16 rounding plus half the float32-angle allowance of
+// tests/attn_oracle.py up to position 131071.
 __device__ __forceinline__ void rotate_pair(
     const bf16* src, bf16* dst, int d, int half, int head_dim, float pos,
     float theta) {
@@ -27,6 +31,55 @@ __device__ __forceinline__ void rotate_pair(
   const float x2 = bf2f(src[d + half]);
   dst[d] = f2bf(x1 * c - x2 * s);
   dst[d + half] = f2bf(x2 * c + x1 * s);
+}
+
+// fp8 cache only: cos and sin of pos · theta^(-2d/head_dim) from a double
+// angle. At 128k positions the angle reaches 1.3e5 rad, where float32 is
+// spaced 2^-7 rad apart and a float32 inv_freq is off by as much again.
+// e4m3 steps are absolute (2^-9) below 2^-6, so a rotated K element near
+// zero landed up to 3 steps from the exact rotation at position 131071 (1
+// step from 8191 on). So inv_freq and the angle are formed in double,
+// reduced there to a fraction of a turn, and the hardware sin/cos (whose
+// argument is in turns) gets that fraction. A thread's pairs share d
+// whenever blockDim.x is a multiple of head_dim/2, so the kernel keeps the
+// last (d, cos, sin).
+struct RopeCosSin {
+  float c;
+  float s;
+};
+
+__device__ __forceinline__ RopeCosSin rope_cos_sin(int d, int head_dim,
+                                                   int pos,
+                                                   double log2_theta) {
+  const double inv_freq =
+      exp2(-2.0 * (double)d / (double)head_dim * log2_theta);
+  double turns = (double)pos * inv_freq * 0.15915494309189535;  // 1/(2π)
+  turns -= floor(turns);
+  const float t = (float)turns;
+  return {__builtin_amdgcn_cosf(t), __builtin_amdgcn_sinf(t)};
+}
+
+// Last (d, cos, sin) a thread computed for its token.
+struct RopeCosSinCache {
+  int d = -1;
+  RopeCosSin cs = {1.0f, 0.0f};
+
+  __device__ __forceinline__ RopeCosSin get(int d_new, int head_dim, int pos,
+                                            double log2_theta) {
+    if (d_new != d) {
+      cs = rope_cos_sin(d_new, head_dim, pos, log2_theta);
+      d = d_new;
+    }
+    return cs;
+  }
+};
+
+__device__ __forceinline__ void rotate_pair_cs(
+    const bf16* src, bf16* dst, int d, int half, RopeCosSin cs) {
+  const float x1 = bf2f(src[d]);
+  const float x2 = bf2f(src[d + half]);
+  dst[d] = f2bf(x1 * cs.c - x2 * cs.s);
+  dst[d + half] = f2bf(x2 * cs.c + x1 * cs.s);
 }
 
 __global__ void rope_kernel(
@@ -114,35 +167,31 @@ __global__ void rope_append_kv_fp8_kernel(
     const int num_kv_heads,
     const int head_dim,
     const int max_seq,
-    const float theta) {
+    const double log2_theta) {
   const int b = blockIdx.x;
   const int pos_i = positions[b];
-  const float pos = (float)pos_i;
   const int half = head_dim / 2;
   const long qkv_row = (long)b * (num_q_heads + 2 * num_kv_heads) * head_dim;
 
   const int rot_total = (num_q_heads + num_kv_heads) * half;
+  RopeCosSinCache cache;
   for (int idx = threadIdx.x; idx < rot_total; idx += blockDim.x) {
     const int head = idx / half;
     const int d = idx % half;
+    const RopeCosSin cs = cache.get(d, head_dim, pos_i, log2_theta);
     if (head < num_q_heads) {
       const bf16* src = qkv + qkv_row + (long)head * head_dim;
       bf16* dst = q_out + ((long)b * num_q_heads + head) * head_dim;
-      rotate_pair(src, dst, d, half, head_dim, pos, theta);
+      rotate_pair_cs(src, dst, d, half, cs);
     } else {
       const int kh = head - num_q_heads;
       const bf16* src = qkv + qkv_row + ((long)num_q_heads + kh) * head_dim;
-      const float inv_freq =
-          __powf(theta, -2.0f * (float)d / (float)head_dim);
-      const float angle = pos * inv_freq;
-      float c, s;
-      __sincosf(angle, &s, &c);
       const float x1 = bf2f(src[d]);
       const float x2 = bf2f(src[d + half]);
       fp8_t* dst = k_cache +
           (((long)b * num_kv_heads + kh) * max_seq + pos_i) * head_dim;
-      dst[d] = f2fp8(x1 * c - x2 * s);
-      dst[d + half] = f2fp8(x2 * c + x1 * s);
+      dst[d] = f2fp8(x1 * cs.c - x2 * cs.s);
+      dst[d + half] = f2fp8(x2 * cs.c + x1 * cs.s);
     }
   }
   // v copy: bf16x2 -> packed 2×e4m3 (adjacent dims), u16 stores
@@ -168,7 +217,7 @@ extern "C" void launch_rope_append_kv_fp8(
   hipLaunchKernelGGL(rope_append_kv_fp8_kernel, grid, block, 0, stream,
                      (const bf16*)qkv, (bf16*)q_out, (fp8_t*)k_cache,
                      (fp8_t*)v_cache, positions, num_q_heads, num_kv_heads,
-                     head_dim, max_seq, theta);
+                     head_dim, max_seq, log2((double)theta));
 }
 
 extern "C" void launch_rope(
