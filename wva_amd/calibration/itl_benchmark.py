@@ -278,3 +278,80 @@ def fit_itl_surface(points) -> Tuple[float, float, float, float]:
     ss_tot = float(((y - y.mean()) ** 2).sum())
     r2 = 1.0 - ss_res / ss_tot if ss_tot > 0 else 1.0
     return alpha, max(beta_eff, 0.0), max(gamma, 0.0), r2
+
+
+# --- chunked prefill (measurement only; not wired into the profile yet) ---
+
+
+def measure_chunked_prefill_tps(
+    model: LlamaDecodeModel,
+    batch: int = 1,
+    seq: int = 2048,
+    chunk: int = 512,
+    iters: int = 3,
+) -> float:
+    """Prefill throughput (prompt tokens/s) when the prompt is prefilled
+    from an empty cache in chunks of `chunk` tokens
+    (model.prefill(chunk_size=chunk)); compare measure_prefill_tps."""
+    seq = min(seq, model.max_seq)
+    batch = min(batch, model.max_batch)
+    tokens = torch.randint(
+        0, model.cfg.vocab_size, (batch, seq), device=model.device
+    )
+    model.prefill(tokens, chunk_size=chunk)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        model.prefill(tokens, chunk_size=chunk)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    return batch * seq * iters / dt
+
+
+def measure_mixed_itl(
+    model: LlamaDecodeModel,
+    decode_batch: int,
+    context_len: int = 512,
+    chunk: int = 512,
+    iters: int = 8,
+    warmup: int = 3,
+) -> float:
+    """Median wall time (ms) of one iteration in which `decode_batch`
+    sequences at `context_len` decode a token while one more sequence,
+    also holding `context_len` cached tokens, prefills a `chunk`-token
+    block (model.mixed_step). chunk=0 times the plain decode_step of the
+    same sequences, the number to compare against. context_lens is put
+    back before every iteration, so each one does the same work."""
+    rows = decode_batch + (1 if chunk else 0)
+    if rows > model.max_batch or context_len + max(chunk, 1) > model.max_seq:
+        raise ValueError("model cache too small for this mixed iteration")
+    model.reset(rows, context_len)
+    lens = model.context_lens.clone()
+    dec = torch.randint(
+        0, model.cfg.vocab_size, (decode_batch,), device=model.device
+    )
+    if chunk:
+        blk = torch.randint(
+            0, model.cfg.vocab_size, (1, chunk), device=model.device
+        )
+
+        def step():
+            model.mixed_step(dec, blk)
+    else:
+        def step():
+            model.decode_step(dec)
+
+    for _ in range(warmup):
+        model.context_lens.copy_(lens)
+        step()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(iters):
+        model.context_lens.copy_(lens)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        step()
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1000.0)
+    times.sort()
+    return times[len(times) // 2]

@@ -279,10 +279,16 @@ class LlamaDecodeModel:
         return logits
 
     @torch.no_grad()
-    def prefill(self, token_ids: torch.Tensor) -> torch.Tensor:
+    def prefill(
+        self, token_ids: torch.Tensor, chunk_size: Optional[int] = None
+    ) -> torch.Tensor:
         """Prefill `token_ids [B, S]`: computes all S positions in one
         pass (causal attention), fills the KV cache, sets context_lens=S
         and returns last-position logits [B, vocab].
+
+        With an integer `chunk_size` the prompt is prefilled from an empty
+        cache in chunks of that many tokens through `prefill_chunk` (the
+        last chunk may be shorter) and the last chunk's logits are returned.
 
         Grounds the ServiceProfile's prefill_tokens_per_s (the TTFT
         model's input) with a measured value instead of a constant.
@@ -292,6 +298,8 @@ class LlamaDecodeModel:
         decode path. RMSNorm/RoPE/SwiGLU reuse the HIP kernels (they are
         row-shaped and batch-size-agnostic).
         """
+        if chunk_size is not None:
+            return self._prefill_chunked(token_ids, int(chunk_size))
         cfg = self.cfg
         if self.weights_dtype != "bf16":
             raise NotImplementedError(
@@ -385,4 +393,132 @@ class LlamaDecodeModel:
         logits = last @ self.lm_head.t()
         self.context_lens.zero_()
         self.context_lens[:B] = S
+        return logits
+
+    # --- chunked prefill: a block of new tokens per sequence attends to a
+    # KV prefix that is already in the cache (vLLM's default scheduling) ---
+
+    def _prefill_chunked(
+        self, token_ids: torch.Tensor, chunk_size: int
+    ) -> torch.Tensor:
+        B, S = token_ids.shape
+        if chunk_size < 1:
+            raise ValueError(f"chunk_size must be >= 1, got {chunk_size}")
+        if S > self.max_seq:
+            raise ValueError(f"S={S} exceeds max_seq={self.max_seq}")
+        self.context_lens.zero_()
+        logits = None
+        for start in range(0, S, chunk_size):
+            logits = self.prefill_chunk(
+                token_ids[:, start:start + chunk_size].contiguous()
+            )
+        return logits
+
+    @torch.no_grad()
+    def prefill_chunk(self, token_ids: torch.Tensor) -> torch.Tensor:
+        """Continue sequences 0..B-1 by a chunk `token_ids [B, C]` from
+        their own `context_lens[b]` (which may differ): the chunk's K/V go
+        to cache rows context_lens[b] .. +C-1, its queries attend to the
+        cached prefix plus the chunk (ops.extend_attn), context_lens[:B]
+        advances by C. Returns the chunk's last-position logits
+        [B, vocab]. Everything per-sequence stays on the device; the
+        caller keeps context_lens[b] + C within max_seq."""
+        return self._chunk_step(None, token_ids)
+
+    @torch.no_grad()
+    def mixed_step(
+        self, decode_tokens: torch.Tensor, chunk_tokens: torch.Tensor
+    ) -> torch.Tensor:
+        """One iteration that mixes decode and chunked prefill: cache rows
+        0..Bd-1 decode one token each (`decode_tokens [Bd]`), rows
+        Bd..Bd+Bp-1 prefill a chunk each (`chunk_tokens [Bp, C]`). All
+        Bd + Bp*C token rows share the norms and linears (one pass over the
+        weights); only attention splits by row range. Returns logits
+        [Bd+Bp, vocab]: the decode rows, then each chunk's last position.
+        context_lens advances by 1 and by C respectively."""
+        return self._chunk_step(decode_tokens, chunk_tokens)
+
+    def _chunk_step(
+        self, decode_tokens: Optional[torch.Tensor], chunk_tokens: torch.Tensor
+    ) -> torch.Tensor:
+        cfg = self.cfg
+        if self.weights_dtype != "bf16":
+            raise NotImplementedError(
+                "chunked prefill with fp8 weights is not implemented"
+            )
+        Bd = 0 if decode_tokens is None else decode_tokens.shape[0]
+        Bp, C = chunk_tokens.shape
+        if C < 1 or C > self.max_seq:
+            raise ValueError(f"chunk of {C} tokens, max_seq={self.max_seq}")
+        if Bd + Bp > self.max_batch:
+            raise ValueError(f"{Bd}+{Bp} sequences, max_batch={self.max_batch}")
+        T = Bp * C
+        Hq, Hk, D = cfg.num_q_heads, cfg.num_kv_heads, cfg.head_dim
+
+        # per-call index tensors, built on the device (no host read)
+        prefix = self.context_lens[Bd:Bd + Bp].clone()  # [Bp] int32
+        pos = prefix[:, None] + torch.arange(
+            C, device=self.device, dtype=torch.int32
+        )  # [Bp, C] absolute positions
+        positions = pos.reshape(-1)
+        # cache rows of the chunk; clamped so that a write stays in the slab
+        row_idx = pos.long().clamp_(max=self.max_seq - 1)
+        seq_idx = torch.arange(Bd, Bd + Bp, device=self.device)[:, None]
+        tokens = chunk_tokens.reshape(-1)
+        if Bd:
+            d_pos = self.context_lens[:Bd].clone()
+            d_ctx = d_pos + 1
+            tokens = torch.cat([decode_tokens, tokens])
+
+        def write_kv(cache, new):  # new [Bp, C, Hk, D], already cache dtype
+            if cache.dtype != self.dtype:  # e4m3: indexed write as bytes
+                cache, new = cache.view(torch.uint8), new.view(torch.uint8)
+            cache[seq_idx, :, row_idx] = new
+
+        x = self.embed.index_select(0, tokens)  # [Bd + T, H]
+        residual: Optional[torch.Tensor] = None
+        for li, layer in enumerate(self.layers):
+            if residual is None:
+                residual = x.clone()
+                h = ops.rmsnorm(x, layer.input_norm, None, cfg.rms_eps)
+            else:
+                h = ops.rmsnorm(x, layer.input_norm, residual, cfg.rms_eps)
+            qkv = h @ layer.wqkv.t()
+
+            q, k, v = qkv[Bd:].split(
+                [cfg.q_size, cfg.kv_size, cfg.kv_size], dim=-1
+            )
+            q = q.reshape(T, Hq, D).contiguous()
+            k = k.reshape(T, Hk, D).contiguous()
+            ops.rope(q, k, positions, cfg.rope_theta)
+            write_kv(self.k_cache[li],
+                     k.reshape(Bp, C, Hk, D).to(self.cache_dtype))
+            write_kv(self.v_cache[li],
+                     v.reshape(Bp, C, Hk, D).to(self.cache_dtype))
+            attn = ops.extend_attn(
+                q, self.k_cache[li][Bd:Bd + Bp], self.v_cache[li][Bd:Bd + Bp],
+                prefix, C, self.scale,
+            ).reshape(T, cfg.q_size)
+            if Bd:
+                qd = ops.rope_append_kv(
+                    qkv[:Bd], self.k_cache[li][:Bd], self.v_cache[li][:Bd],
+                    d_pos, Hq, Hk, cfg.rope_theta,
+                )
+                attn_d = ops.gqa_decode_attn(
+                    qd, self.k_cache[li][:Bd], self.v_cache[li][:Bd], d_ctx,
+                    self.scale,
+                )
+                attn = torch.cat([attn_d.reshape(Bd, cfg.q_size), attn])
+            x = attn @ layer.wo.t()
+
+            h2 = ops.rmsnorm(x, layer.post_attn_norm, residual, cfg.rms_eps)
+            gate_up = h2 @ layer.w_gate_up.t()
+            act = ops.silu_mul_fused(gate_up)
+            x = act @ layer.w_down.t()
+
+        final = ops.rmsnorm(x, self.final_norm, residual, cfg.rms_eps)
+        last = final[Bd:].reshape(Bp, C, cfg.hidden_size)[:, -1]
+        logits = torch.cat([final[:Bd], last]) @ self.lm_head.t()
+        self.context_lens[:Bd] += 1
+        self.context_lens[Bd:Bd + Bp] += C
         return logits

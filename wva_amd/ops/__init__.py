@@ -132,6 +132,38 @@ def gqa_decode_attn_ref(
     return out
 
 
+def extend_attn_ref(
+    q: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    prefix_lens: torch.Tensor,
+    chunk: int,
+    scale: float,
+):
+    """fp32 reference of chunked-prefill attention. q [B*chunk, Hq, D];
+    sequence b's chunk sits at positions P_b .. P_b+chunk-1 of the
+    head-major caches [B, Hk, S, D] (P_b = prefix_lens[b]); query i sees
+    key kp iff kp <= P_b + i. Rows at or past P_b + chunk are never read."""
+    T, Hq, D = q.shape
+    Hk = k_cache.shape[1]
+    G = Hq // Hk
+    B = T // chunk
+    qf = q.float().reshape(B, chunk, Hk, G, D)
+    out = torch.zeros(B, chunk, Hk, G, D, dtype=torch.float32, device=q.device)
+    rows = torch.arange(chunk, device=q.device)
+    for b in range(B):
+        p0 = int(prefix_lens[b])
+        n = p0 + chunk
+        k = k_cache[b, :, :n].float()  # [Hk, n, D]
+        v = v_cache[b, :, :n].float()
+        scores = torch.einsum("qhgd,hsd->hgqs", qf[b], k) * scale
+        seen = torch.arange(n, device=q.device)[None, :] <= (p0 + rows)[:, None]
+        scores = scores.masked_fill(~seen, float("-inf"))
+        p = torch.softmax(scores, dim=-1)
+        out[b] = torch.einsum("hgqs,hsd->qhgd", p, v)
+    return out.reshape(T, Hq, D)
+
+
 def moe_route_ref(router_logits: torch.Tensor, top_k: int):
     """MoE routing reference.
 
@@ -471,3 +503,24 @@ def prefill_attn(
     calibration/model.py's matmul branch.
     """
     return _require_ext().prefill_attn(q, k_cache, v_cache, batch, seq, scale)
+
+
+def extend_attn(
+    q: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    prefix_lens: torch.Tensor,
+    chunk: int,
+    scale: float,
+) -> torch.Tensor:
+    """Chunked-prefill attention: `chunk` new query rows per sequence over
+    a cached prefix. q [B*chunk, Hq, 128]; the caches already hold sequence
+    b's prefix and its chunk at rows prefix_lens[b] .. prefix_lens[b] +
+    chunk - 1. prefix_lens [B] is read on the device (no host sync)."""
+    if q.is_cuda:
+        return _require_ext().extend_attn(
+            q, k_cache, v_cache, prefix_lens.to(torch.int32), chunk, scale
+        )
+    return extend_attn_ref(q, k_cache, v_cache, prefix_lens, chunk, scale).to(
+        q.dtype
+    )

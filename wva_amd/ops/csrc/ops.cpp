@@ -43,6 +43,12 @@ extern "C" void launch_prefill_attn_ex(void* out, const void* q,
                                        int num_kv_heads, int max_seq,
                                        float scale, int kv_fp8,
                                        hipStream_t stream);
+extern "C" void launch_extend_attn(void* out, const void* q,
+                                   const void* k_cache, const void* v_cache,
+                                   const int* prefix_lens, int batch,
+                                   int chunk, int num_q_heads,
+                                   int num_kv_heads, int max_seq, float scale,
+                                   int kv_fp8, hipStream_t stream);
 extern "C" int skinny_gemm_tile_n(int M);
 extern "C" void launch_skinny_gemm(void* c, void* ws, const void* a,
                                    const void* w, int M, int N, int K,
@@ -366,6 +372,43 @@ void check_i32_contig(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
+// Chunked prefill ("extend") attention: `chunk` new query rows per sequence
+// attend to a cached prefix of prefix_lens[b] rows plus the chunk's own
+// rows, which the caller has already written at prefix_lens[b] ..
+// prefix_lens[b]+chunk-1 (csrc/prefill_attention.hip, HAS_PREFIX).
+// q/out: [B*chunk, Hq, 128]; prefix_lens stays on the device.
+torch::Tensor extend_attn(torch::Tensor q, torch::Tensor k_cache,
+                          torch::Tensor v_cache, torch::Tensor prefix_lens,
+                          int64_t chunk, double scale) {
+  check_bf16_contig(q, "q");
+  const bool kv_fp8 = check_cache_contig(k_cache, "k_cache");
+  TORCH_CHECK(check_cache_contig(v_cache, "v_cache") == kv_fp8,
+              "k/v cache dtype mismatch");
+  check_i32_contig(prefix_lens, "prefix_lens");
+  TORCH_CHECK(q.dim() == 3 && q.size(2) == 128, "q must be [T, Hq, 128]");
+  TORCH_CHECK(chunk >= 1 && q.size(0) % chunk == 0,
+              "T must be a multiple of chunk");
+  const int64_t batch = q.size(0) / chunk;
+  TORCH_CHECK(prefix_lens.dim() == 1 && prefix_lens.size(0) == batch,
+              "prefix_lens must be [B] with B = T / chunk");
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(3) == 128,
+              "k_cache must be [B, Hk, S_max, 128]");
+  TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), "k/v cache shape mismatch");
+  TORCH_CHECK(k_cache.size(0) >= batch, "cache holds fewer than B sequences");
+  const int num_q_heads = q.size(1);
+  const int num_kv_heads = k_cache.size(1);
+  const int max_seq = k_cache.size(2);
+  TORCH_CHECK(chunk <= max_seq, "chunk exceeds cache size");
+  TORCH_CHECK(num_q_heads % num_kv_heads == 0, "Hq must divide by Hk");
+  TORCH_CHECK(num_q_heads / num_kv_heads <= 8, "GQA group size must be <= 8");
+  auto out = torch::empty_like(q);
+  launch_extend_attn(out.data_ptr(), q.data_ptr(), k_cache.data_ptr(),
+                     v_cache.data_ptr(), prefix_lens.data_ptr<int>(),
+                     (int)batch, (int)chunk, num_q_heads, num_kv_heads,
+                     max_seq, (float)scale, kv_fp8 ? 1 : 0, current_stream());
+  return out;
+}
+
 // The m-tile grid dimension is launched at its static bound; keep it (and
 // every int index the kernels form) comfortably in range.
 void check_moe_sizes(long T, long E, long K) {
@@ -515,6 +558,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Causal flash-attention prefill over head-major KV caches",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("batch"), py::arg("seq"), py::arg("scale"));
+  m.def("extend_attn", &extend_attn,
+        "Chunked-prefill attention: a chunk of query rows per sequence over "
+        "a cached prefix (device-side prefix_lens)",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("prefix_lens"), py::arg("chunk"), py::arg("scale"));
   m.def("skinny_linear_fp8", &skinny_linear_fp8,
         "Weight-only fp8 decode GEMM: x[M,K]bf16 @ w[N,K]e4m3^T, M <= 64",
         py::arg("x"), py::arg("w"), py::arg("w_scale"));

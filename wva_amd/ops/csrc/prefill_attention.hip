@@ -54,14 +54,26 @@ __device__ __forceinline__ float group16_sum(float v) {
   return v;
 }
 
-template <bool KV_FP8>
+// HAS_PREFIX (chunked prefill, "extend"): the S query rows of sequence b
+// are a chunk that sits at absolute positions P_b .. P_b+S-1, with
+// P_b = prefix_lens[b] read on the device; the caches already hold the
+// prefix and the chunk's own rows. Query i sees key kp iff kp <= P_b + i.
+// The kv tiles stay aligned at 0, so a row goes through the same tile
+// sequence however the prompt was chunked; the q-tile is then unaligned to
+// them and its diagonal may cross two tiles, which the per-element mask
+// (applied on every tile) covers. P_b and the live row count are clamped
+// to the slab, so no content of prefix_lens can take a load out of it.
+// Without HAS_PREFIX, P_b is the constant 0 and the kernel is the
+// one-shot prefill.
+template <bool KV_FP8, bool HAS_PREFIX>
 __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
     bf16* __restrict__ out,            // [T, Hq, 128]
     const bf16* __restrict__ q,        // [T, Hq, 128]
     const void* __restrict__ k_cache,  // [B, Hk, S_max, 128] bf16|e4m3
     const void* __restrict__ v_cache,
+    const int* __restrict__ prefix_lens,  // [B], HAS_PREFIX only
     const int B,
-    const int S,
+    const int S,                       // query rows per sequence
     const int num_q_heads,
     const int num_kv_heads,
     const int max_seq,
@@ -72,6 +84,15 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
   const int kvh = h / (num_q_heads / num_kv_heads);
   const int qt0 = blockIdx.y * QT;     // first query position of the tile
   if (qt0 >= S) return;
+
+  // first absolute position of the chunk, and rows of the slab that are
+  // live (prefix + chunk); rows at or past kv_len may hold anything
+  int q_pos0 = 0;
+  int kv_len = S;
+  if constexpr (HAS_PREFIX) {
+    q_pos0 = min(max(prefix_lens[b], 0), max_seq);
+    kv_len = min(q_pos0 + S, max_seq);
+  }
 
   const int lane = threadIdx.x & (WAVE_SIZE - 1);
   const int wave = threadIdx.x / WAVE_SIZE;
@@ -130,10 +151,11 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
 #pragma unroll
   for (int n = 0; n < 8; ++n) o_acc[n] = f32x4_frag{0.f, 0.f, 0.f, 0.f};
 
-  const int kv_end = qt0 + QT < S ? qt0 + QT : S;  // causal upper bound
+  // causal upper bound of this q-tile's sweep
+  const int kv_end = min(q_pos0 + qt0 + QT, kv_len);
 
   for (int kt0 = 0; kt0 < kv_end; kt0 += KT_POS) {
-    const int kn = min(KT_POS, S - kt0);
+    const int kn = min(KT_POS, kv_len - kt0);
 
     // --- stage V tile transposed (cooperative, all waves): each
     // thread reads one dim-pair at one position (coalesced along the
@@ -206,8 +228,8 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
     }
 
     // --- causal mask + online softmax on the fragments ---
-    // element (reg i, n-tile nt): q-row r = qt0 + 16·wave + (lane>>4)·4+i,
-    // k-pos = kt0 + 16·nt + (lane&15)
+    // element (reg i, n-tile nt): q-row r = qt0 + 16·wave + (lane>>4)·4+i
+    // at absolute position q_pos0 + r, k-pos = kt0 + 16·nt + (lane&15)
     float tile_max[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) tile_max[i] = -INFINITY;
@@ -218,7 +240,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
         const int qr = qt0 + 16 * wave + (lane >> 4) * 4 + i;
         const int kp = kt0 + 16 * nt + (lane & 15);
         float v = s_frag[nt][i] * scale;
-        if (kp > qr || kp >= kn + kt0 || qr >= S) v = -INFINITY;
+        if (kp > q_pos0 + qr || kp >= kn + kt0 || qr >= S) v = -INFINITY;
         s_frag[nt][i] = v;
         tile_max[i] = fmaxf(tile_max[i], v);
       }
@@ -332,19 +354,44 @@ extern "C" void launch_prefill_attn(
                          num_kv_heads, max_seq, scale, 0, stream);
 }
 
+template <bool HAS_PREFIX>
+static void launch_prefill_kernel(
+    void* out, const void* q, const void* k_cache, const void* v_cache,
+    const int* prefix_lens, int batch, int rows, int num_q_heads,
+    int num_kv_heads, int max_seq, float scale, int kv_fp8,
+    hipStream_t stream) {
+  dim3 grid(batch * num_q_heads, (rows + QT - 1) / QT);
+  dim3 block(256);
+  if (kv_fp8) {
+    hipLaunchKernelGGL((prefill_attn_kernel<true, HAS_PREFIX>), grid, block,
+                       0, stream, (bf16*)out, (const bf16*)q, k_cache,
+                       v_cache, prefix_lens, batch, rows, num_q_heads,
+                       num_kv_heads, max_seq, scale);
+  } else {
+    hipLaunchKernelGGL((prefill_attn_kernel<false, HAS_PREFIX>), grid, block,
+                       0, stream, (bf16*)out, (const bf16*)q, k_cache,
+                       v_cache, prefix_lens, batch, rows, num_q_heads,
+                       num_kv_heads, max_seq, scale);
+  }
+}
+
 extern "C" void launch_prefill_attn_ex(
     void* out, const void* q, const void* k_cache, const void* v_cache,
     int batch, int seq, int num_q_heads, int num_kv_heads, int max_seq,
     float scale, int kv_fp8, hipStream_t stream) {
-  dim3 grid(batch * num_q_heads, (seq + QT - 1) / QT);
-  dim3 block(256);
-  if (kv_fp8) {
-    hipLaunchKernelGGL(prefill_attn_kernel<true>, grid, block, 0, stream,
-                       (bf16*)out, (const bf16*)q, k_cache, v_cache, batch,
-                       seq, num_q_heads, num_kv_heads, max_seq, scale);
-  } else {
-    hipLaunchKernelGGL(prefill_attn_kernel<false>, grid, block, 0, stream,
-                       (bf16*)out, (const bf16*)q, k_cache, v_cache, batch,
-                       seq, num_q_heads, num_kv_heads, max_seq, scale);
-  }
+  launch_prefill_kernel<false>(out, q, k_cache, v_cache, nullptr, batch, seq,
+                               num_q_heads, num_kv_heads, max_seq, scale,
+                               kv_fp8, stream);
+}
+
+// Chunked prefill: `chunk` query rows per sequence at the device-side
+// offsets prefix_lens[b]; grid = (B·Hq, ceil(chunk/64)).
+extern "C" void launch_extend_attn(
+    void* out, const void* q, const void* k_cache, const void* v_cache,
+    const int* prefix_lens, int batch, int chunk, int num_q_heads,
+    int num_kv_heads, int max_seq, float scale, int kv_fp8,
+    hipStream_t stream) {
+  launch_prefill_kernel<true>(out, q, k_cache, v_cache, prefix_lens, batch,
+                              chunk, num_q_heads, num_kv_heads, max_seq,
+                              scale, kv_fp8, stream);
 }
