@@ -15,7 +15,7 @@ from __future__ import annotations
 import json
 import time
 from dataclasses import asdict, dataclass
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -351,6 +351,54 @@ def measure_mixed_itl(
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         step()
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1000.0)
+    times.sort()
+    return times[len(times) // 2]
+
+
+def measure_ragged_itl(
+    model: LlamaDecodeModel,
+    decode_batch: int,
+    context_len: int,
+    chunk_lens: Sequence[int],
+    iters: int = 8,
+    warmup: int = 3,
+) -> float:
+    """Median wall time (ms) of one iteration in which `decode_batch`
+    sequences at `context_len` decode a token while len(chunk_lens) more
+    sequences, each holding `context_len` cached tokens, prefill chunks of
+    the given unequal lengths in one model.ragged_step. context_lens is put
+    back before every iteration, so each one does the same work."""
+    chunk_lens = [int(n) for n in chunk_lens]
+    rows = decode_batch + len(chunk_lens)
+    if not chunk_lens or min(chunk_lens) < 0 or sum(chunk_lens) < 1:
+        raise ValueError("chunk_lens must hold at least one token")
+    max_chunk = max(chunk_lens)
+    if rows > model.max_batch or context_len + max_chunk > model.max_seq:
+        raise ValueError("model cache too small for this ragged iteration")
+    model.reset(rows, context_len)
+    lens = model.context_lens.clone()
+    dec = None
+    if decode_batch:
+        dec = torch.randint(
+            0, model.cfg.vocab_size, (decode_batch,), device=model.device
+        )
+    blk = torch.randint(
+        0, model.cfg.vocab_size, (sum(chunk_lens),), device=model.device
+    )
+    c_lens = torch.tensor(chunk_lens, dtype=torch.int32, device=model.device)
+
+    for _ in range(warmup):
+        model.context_lens.copy_(lens)
+        model.ragged_step(dec, blk, c_lens, max_chunk)
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(iters):
+        model.context_lens.copy_(lens)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        model.ragged_step(dec, blk, c_lens, max_chunk)
         torch.cuda.synchronize()
         times.append((time.perf_counter() - t0) * 1000.0)
     times.sort()

@@ -453,7 +453,7 @@ class LlamaDecodeModel:
         if Bd + Bp > self.max_batch:
             raise ValueError(f"{Bd}+{Bp} sequences, max_batch={self.max_batch}")
         T = Bp * C
-        Hq, Hk, D = cfg.num_q_heads, cfg.num_kv_heads, cfg.head_dim
+        Hk, D = cfg.num_kv_heads, cfg.head_dim
 
         # per-call index tensors, built on the device (no host read)
         prefix = self.context_lens[Bd:Bd + Bp].clone()  # [Bp] int32
@@ -466,8 +466,6 @@ class LlamaDecodeModel:
         seq_idx = torch.arange(Bd, Bd + Bp, device=self.device)[:, None]
         tokens = chunk_tokens.reshape(-1)
         if Bd:
-            d_pos = self.context_lens[:Bd].clone()
-            d_ctx = d_pos + 1
             tokens = torch.cat([decode_tokens, tokens])
 
         def write_kv(cache, new):  # new [Bp, C, Hk, D], already cache dtype
@@ -475,6 +473,35 @@ class LlamaDecodeModel:
                 cache, new = cache.view(torch.uint8), new.view(torch.uint8)
             cache[seq_idx, :, row_idx] = new
 
+        def chunk_attn(li, q, k, v):
+            write_kv(self.k_cache[li],
+                     k.reshape(Bp, C, Hk, D).to(self.cache_dtype))
+            write_kv(self.v_cache[li],
+                     v.reshape(Bp, C, Hk, D).to(self.cache_dtype))
+            return ops.extend_attn(
+                q, self.k_cache[li][Bd:Bd + Bp], self.v_cache[li][Bd:Bd + Bp],
+                prefix, C, self.scale,
+            )
+
+        final = self._mixed_layers(tokens, Bd, T, positions, chunk_attn)
+        last = final[Bd:].reshape(Bp, C, cfg.hidden_size)[:, -1]
+        logits = torch.cat([final[:Bd], last]) @ self.lm_head.t()
+        self.context_lens[:Bd] += 1
+        self.context_lens[Bd:Bd + Bp] += C
+        return logits
+
+    def _mixed_layers(self, tokens, Bd, T, positions, chunk_attn):
+        """The layer loop of one mixed iteration over `tokens [Bd + T]`:
+        rows 0..Bd-1 decode on cache rows 0..Bd-1 (rope_append_kv +
+        gqa_decode_attn), rows Bd.. are T prefill rows at `positions [T]`
+        whose K/V write and attention are `chunk_attn(li, q, k, v)` (q, k
+        roped [T, H*, D], v [T, Hk, D]) -> [T, Hq, D]. Norms and linears
+        run once over all rows. Returns the final-normed hidden states."""
+        cfg = self.cfg
+        Hq, Hk, D = cfg.num_q_heads, cfg.num_kv_heads, cfg.head_dim
+        if Bd:
+            d_pos = self.context_lens[:Bd].clone()
+            d_ctx = d_pos + 1
         x = self.embed.index_select(0, tokens)  # [Bd + T, H]
         residual: Optional[torch.Tensor] = None
         for li, layer in enumerate(self.layers):
@@ -491,14 +518,9 @@ class LlamaDecodeModel:
             q = q.reshape(T, Hq, D).contiguous()
             k = k.reshape(T, Hk, D).contiguous()
             ops.rope(q, k, positions, cfg.rope_theta)
-            write_kv(self.k_cache[li],
-                     k.reshape(Bp, C, Hk, D).to(self.cache_dtype))
-            write_kv(self.v_cache[li],
-                     v.reshape(Bp, C, Hk, D).to(self.cache_dtype))
-            attn = ops.extend_attn(
-                q, self.k_cache[li][Bd:Bd + Bp], self.v_cache[li][Bd:Bd + Bp],
-                prefix, C, self.scale,
-            ).reshape(T, cfg.q_size)
+            attn = chunk_attn(li, q, k, v.reshape(T, Hk, D)).reshape(
+                T, cfg.q_size
+            )
             if Bd:
                 qd = ops.rope_append_kv(
                     qkv[:Bd], self.k_cache[li][:Bd], self.v_cache[li][:Bd],
@@ -516,9 +538,78 @@ class LlamaDecodeModel:
             act = ops.silu_mul_fused(gate_up)
             x = act @ layer.w_down.t()
 
-        final = ops.rmsnorm(x, self.final_norm, residual, cfg.rms_eps)
-        last = final[Bd:].reshape(Bp, C, cfg.hidden_size)[:, -1]
+        return ops.rmsnorm(x, self.final_norm, residual, cfg.rms_eps)
+
+    @torch.no_grad()
+    def ragged_step(
+        self,
+        decode_tokens: Optional[torch.Tensor],
+        chunk_tokens: torch.Tensor,
+        chunk_lens: torch.Tensor,
+        max_chunk: int,
+    ) -> torch.Tensor:
+        """One iteration with chunks of unequal length: cache rows 0..Bd-1
+        decode one token each (`decode_tokens [Bd]` or None), rows
+        Bd..Bd+Bp-1 each continue by chunk_lens[b] tokens from their own
+        context_lens. `chunk_tokens [T]` packs the chunks one after another
+        (T >= sum of chunk_lens >= 1; rows past that sum are computed but
+        written nowhere), `chunk_lens [Bp]` is int32 on the device and `max_chunk`
+        its host-side upper bound. All Bd + T token rows share the norms and
+        linears; the chunks share one ops.extend_attn_ragged launch per
+        layer. Nothing per-sequence is read on the host. Returns logits
+        [Bd+Bp, vocab]: the decode rows, then each sequence's last chunk row
+        (unspecified for a sequence with chunk_lens[b] == 0, whose
+        context_lens and cache rows stay as they are). context_lens advances
+        by 1 and by chunk_lens respectively; the caller keeps
+        context_lens[b] + chunk_lens[b] within max_seq."""
+        if self.weights_dtype != "bf16":
+            raise NotImplementedError(
+                "chunked prefill with fp8 weights is not implemented"
+            )
+        Bd = 0 if decode_tokens is None else decode_tokens.shape[0]
+        Bp, T = chunk_lens.shape[0], chunk_tokens.shape[0]
+        if max_chunk < 1 or max_chunk > self.max_seq:
+            raise ValueError(
+                f"max_chunk={max_chunk}, max_seq={self.max_seq}")
+        if Bp < 1 or T < 1:
+            raise ValueError("ragged_step needs a chunk sequence and a row")
+        if Bd + Bp > self.max_batch:
+            raise ValueError(f"{Bd}+{Bp} sequences, max_batch={self.max_batch}")
+
+        # per-row sequence index and position, built on the device
+        lens = chunk_lens.to(torch.int32).clamp(0, max_chunk)
+        ends = torch.cumsum(lens, 0)             # int64
+        q_starts = ends - lens
+        prefix = self.context_lens[Bd:Bd + Bp].clone()  # [Bp] int32
+        rows = torch.arange(T, device=self.device)
+        owned = rows < ends[-1]
+        # a row past the packed chunks rewrites row 0's K/V at row 0's place
+        src = torch.where(owned, rows, torch.zeros_like(rows))
+        seq = torch.searchsorted(ends, src, right=True).clamp_(max=Bp - 1)
+        pos = prefix[seq] + (src - q_starts[seq])  # [T] absolute positions
+        positions = pos.to(torch.int32)
+        row_idx = pos.long().clamp_(max=self.max_seq - 1)
+        seq_idx = seq + Bd
+        tokens = chunk_tokens
+        if Bd:
+            tokens = torch.cat([decode_tokens, tokens])
+
+        def write_kv(cache, new):  # new [T, Hk, D], already cache dtype
+            if cache.dtype != self.dtype:  # e4m3: indexed write as bytes
+                cache, new = cache.view(torch.uint8), new.view(torch.uint8)
+            cache[seq_idx, :, row_idx] = new.index_select(0, src)
+
+        def chunk_attn(li, q, k, v):
+            write_kv(self.k_cache[li], k.to(self.cache_dtype))
+            write_kv(self.v_cache[li], v.to(self.cache_dtype))
+            return ops.extend_attn_ragged(
+                q, self.k_cache[li][Bd:Bd + Bp], self.v_cache[li][Bd:Bd + Bp],
+                prefix, lens, max_chunk, self.scale,
+            )
+
+        final = self._mixed_layers(tokens, Bd, T, positions, chunk_attn)
+        last = final[Bd:].index_select(0, (ends - 1).clamp_(0, T - 1))
         logits = torch.cat([final[:Bd], last]) @ self.lm_head.t()
         self.context_lens[:Bd] += 1
-        self.context_lens[Bd:Bd + Bp] += C
+        self.context_lens[Bd:Bd + Bp] += lens
         return logits

@@ -164,6 +164,35 @@ def extend_attn_ref(
     return out.reshape(T, Hq, D)
 
 
+def extend_attn_ragged_ref(
+    q: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    prefix_lens: torch.Tensor,
+    chunk_lens: torch.Tensor,
+    max_chunk: int,
+    scale: float,
+):
+    """fp32 reference of ragged chunked-prefill attention. q is packed
+    [T, Hq, D]: sequence b owns the chunk_lens[b] <= max_chunk rows from the
+    exclusive cumsum of chunk_lens and sits at positions P_b .. P_b+len_b-1
+    (P_b = prefix_lens[b]). Per sequence it is extend_attn_ref with B = 1
+    and chunk = len_b, so cache rows at or past P_b + len_b are never read;
+    rows of q that no sequence owns give 0."""
+    T, Hq, D = q.shape
+    out = torch.zeros(T, Hq, D, dtype=torch.float32, device=q.device)
+    start = 0
+    for b, n in enumerate(chunk_lens.tolist()):
+        n = min(max(int(n), 0), max_chunk, T - start)
+        if n:
+            out[start:start + n] = extend_attn_ref(
+                q[start:start + n], k_cache[b:b + 1], v_cache[b:b + 1],
+                prefix_lens[b:b + 1], n, scale,
+            )
+        start += n
+    return out
+
+
 def moe_route_ref(router_logits: torch.Tensor, top_k: int):
     """MoE routing reference.
 
@@ -523,4 +552,52 @@ def extend_attn(
         )
     return extend_attn_ref(q, k_cache, v_cache, prefix_lens, chunk, scale).to(
         q.dtype
+    )
+
+
+def extend_attn_ragged(
+    q: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    prefix_lens: torch.Tensor,
+    chunk_lens: torch.Tensor,
+    max_chunk: int,
+    scale: float,
+    num_splits: Optional[int] = None,
+) -> torch.Tensor:
+    """Ragged chunked-prefill attention: one launch for sequences whose
+    chunks differ in length. q is packed [T, Hq, 128]; sequence b owns the
+    chunk_lens[b] rows that start at the exclusive cumsum of chunk_lens and
+    continues from prefix_lens[b] (its K/V already in the caches at rows
+    prefix_lens[b] .. + chunk_lens[b] - 1). `max_chunk` is a host-side upper
+    bound of chunk_lens that sizes the launch; prefix_lens, chunk_lens and
+    the row starts stay on the device (no host sync, graph-capturable).
+    Rows of q that no sequence owns come back as 0. `num_splits` forces the
+    split-KV factor; None asks extend_attn_ragged_num_splits."""
+    if q.is_cuda:
+        if num_splits is None:
+            num_splits = extend_attn_ragged_num_splits(
+                chunk_lens.shape[0], q.shape[1], max_chunk, k_cache.shape[2]
+            )
+        lens = chunk_lens.to(torch.int32)
+        q_starts = torch.cumsum(lens, 0, dtype=torch.int32) - lens
+        return _require_ext().extend_attn_ragged(
+            q, k_cache, v_cache, prefix_lens.to(torch.int32), q_starts, lens,
+            max_chunk, scale, num_splits,
+        )
+    return extend_attn_ragged_ref(
+        q, k_cache, v_cache, prefix_lens, chunk_lens, max_chunk, scale
+    ).to(q.dtype)
+
+
+def extend_attn_ragged_num_splits(
+    batch: int, num_q_heads: int, max_chunk: int, max_seq: int
+) -> int:
+    """Split-KV factor extend_attn_ragged picks for `batch` sequences of at
+    most `max_chunk` rows over a [*, *, max_seq, 128] cache (1 = unsplit, no
+    merge). Static shapes only."""
+    return int(
+        _require_ext().extend_attn_ragged_splits(
+            batch, num_q_heads, max_chunk, max_seq
+        )
     )

@@ -49,6 +49,14 @@ extern "C" void launch_extend_attn(void* out, const void* q,
                                    int chunk, int num_q_heads,
                                    int num_kv_heads, int max_seq, float scale,
                                    int kv_fp8, hipStream_t stream);
+extern "C" int extend_attn_ragged_num_splits(int batch, int num_q_heads,
+                                             int max_chunk, int max_seq);
+extern "C" void launch_extend_attn_ragged(
+    void* out, void* ws, const void* q, const void* k_cache,
+    const void* v_cache, const int* prefix_lens, const int* q_starts,
+    const int* chunk_lens, int batch, int total_rows, int max_chunk,
+    int num_q_heads, int num_kv_heads, int max_seq, int num_splits,
+    float scale, int kv_fp8, hipStream_t stream);
 extern "C" int skinny_gemm_tile_n(int M);
 extern "C" void launch_skinny_gemm(void* c, void* ws, const void* a,
                                    const void* w, int M, int N, int K,
@@ -409,6 +417,77 @@ torch::Tensor extend_attn(torch::Tensor q, torch::Tensor k_cache,
   return out;
 }
 
+// Ragged chunked prefill: sequence b owns the chunk_lens[b] <= max_chunk
+// packed rows of q from q_starts[b] and continues from prefix_lens[b]; all
+// three stay on the device (csrc/prefill_attention.hip, RAGGED). q/out:
+// [T, Hq, 128]; rows that no sequence owns read as 0. num_splits > 1 splits
+// the kv sweep over a workspace and merges (extend_attn_ragged_splits gives
+// the launch heuristic's count).
+torch::Tensor extend_attn_ragged(torch::Tensor q, torch::Tensor k_cache,
+                                 torch::Tensor v_cache,
+                                 torch::Tensor prefix_lens,
+                                 torch::Tensor q_starts,
+                                 torch::Tensor chunk_lens, int64_t max_chunk,
+                                 double scale, int64_t num_splits) {
+  check_bf16_contig(q, "q");
+  const bool kv_fp8 = check_cache_contig(k_cache, "k_cache");
+  TORCH_CHECK(check_cache_contig(v_cache, "v_cache") == kv_fp8,
+              "k/v cache dtype mismatch");
+  check_i32_contig(prefix_lens, "prefix_lens");
+  check_i32_contig(q_starts, "q_starts");
+  check_i32_contig(chunk_lens, "chunk_lens");
+  TORCH_CHECK(q.dim() == 3 && q.size(2) == 128, "q must be [T, Hq, 128]");
+  TORCH_CHECK(q.size(0) >= 1, "need at least one query row");
+  TORCH_CHECK(chunk_lens.dim() == 1 && chunk_lens.size(0) >= 1,
+              "chunk_lens must be [B] with B >= 1");
+  const int64_t batch = chunk_lens.size(0);
+  TORCH_CHECK(prefix_lens.dim() == 1 && prefix_lens.size(0) == batch,
+              "prefix_lens must be [B] like chunk_lens");
+  TORCH_CHECK(q_starts.dim() == 1 && q_starts.size(0) == batch,
+              "q_starts must be [B] like chunk_lens");
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(3) == 128,
+              "k_cache must be [B, Hk, S_max, 128]");
+  TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), "k/v cache shape mismatch");
+  TORCH_CHECK(k_cache.size(0) >= batch, "cache holds fewer than B sequences");
+  const int num_q_heads = q.size(1);
+  const int num_kv_heads = k_cache.size(1);
+  const int max_seq = k_cache.size(2);
+  TORCH_CHECK(max_chunk >= 1 && max_chunk <= max_seq,
+              "max_chunk must be in [1, cache size]");
+  TORCH_CHECK(num_q_heads % num_kv_heads == 0, "Hq must divide by Hk");
+  TORCH_CHECK(num_q_heads / num_kv_heads <= 8, "GQA group size must be <= 8");
+  TORCH_CHECK(q.size(0) < (1L << 31) / num_q_heads, "T * Hq too large");
+  const int64_t tiles = (max_chunk + 63) / 64;
+  TORCH_CHECK(tiles <= 65535 && batch * num_q_heads < (1L << 31),
+              "launch grid too large");
+  TORCH_CHECK(num_splits >= 1 && num_splits <= 65535,
+              "num_splits must be in [1, 65535]");
+  auto out = torch::zeros_like(q);
+  torch::Tensor ws;
+  void* ws_ptr = nullptr;
+  if (num_splits > 1) {
+    const int64_t floats =
+        batch * num_q_heads * tiles * 64 * num_splits * (2 + 128);
+    TORCH_CHECK(floats <= (1L << 28),
+                "split workspace would exceed 1 GiB; use fewer splits");
+    ws = torch::empty({floats}, q.options().dtype(torch::kFloat32));
+    ws_ptr = ws.data_ptr();
+  }
+  launch_extend_attn_ragged(
+      out.data_ptr(), ws_ptr, q.data_ptr(), k_cache.data_ptr(),
+      v_cache.data_ptr(), prefix_lens.data_ptr<int>(),
+      q_starts.data_ptr<int>(), chunk_lens.data_ptr<int>(), (int)batch,
+      (int)q.size(0), (int)max_chunk, num_q_heads, num_kv_heads, max_seq,
+      (int)num_splits, (float)scale, kv_fp8 ? 1 : 0, current_stream());
+  return out;
+}
+
+int64_t extend_attn_ragged_splits(int64_t batch, int64_t num_q_heads,
+                                  int64_t max_chunk, int64_t max_seq) {
+  return extend_attn_ragged_num_splits((int)batch, (int)num_q_heads,
+                                       (int)max_chunk, (int)max_seq);
+}
+
 // The m-tile grid dimension is launched at its static bound; keep it (and
 // every int index the kernels form) comfortably in range.
 void check_moe_sizes(long T, long E, long K) {
@@ -563,6 +642,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "a cached prefix (device-side prefix_lens)",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("prefix_lens"), py::arg("chunk"), py::arg("scale"));
+  m.def("extend_attn_ragged", &extend_attn_ragged,
+        "Ragged chunked-prefill attention: chunk_lens[b] packed query rows "
+        "per sequence from q_starts[b] over a cached prefix, optional "
+        "split-KV (all per-sequence tensors on the device)",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("prefix_lens"), py::arg("q_starts"), py::arg("chunk_lens"),
+        py::arg("max_chunk"), py::arg("scale"), py::arg("num_splits"));
+  m.def("extend_attn_ragged_splits", &extend_attn_ragged_splits,
+        "Split-KV factor extend_attn_ragged picks for these static shapes",
+        py::arg("batch"), py::arg("num_q_heads"), py::arg("max_chunk"),
+        py::arg("max_seq"));
   m.def("skinny_linear_fp8", &skinny_linear_fp8,
         "Weight-only fp8 decode GEMM: x[M,K]bf16 @ w[N,K]e4m3^T, M <= 64",
         py::arg("x"), py::arg("w"), py::arg("w_scale"));

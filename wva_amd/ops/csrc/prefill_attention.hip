@@ -65,7 +65,41 @@ __device__ __forceinline__ float group16_sum(float v) {
 // to the slab, so no content of prefix_lens can take a load out of it.
 // Without HAS_PREFIX, P_b is the constant 0 and the kernel is the
 // one-shot prefill.
-template <bool KV_FP8, bool HAS_PREFIX>
+//
+// RAGGED (implies HAS_PREFIX): q/out are packed [T, Hq, 128] and sequence b
+// owns the len_b = chunk_lens[b] rows from q_starts[b]; S is only the static
+// upper bound of len_b that sized the grid, so a workgroup whose q-tile
+// starts at or past len_b returns, and the live cache rows end at
+// P_b + len_b. blockIdx.z is a split of the kv sweep: split s of N walks
+// the tiles s, s+N, s+2N, ... below the q-tile's own kv_end (the decode
+// kernels' interleaving; it balances whatever the lengths are). N == 1
+// stores the normalised output as the other modes do; N > 1 stores the
+// unnormalised (m, s, o[128]) of every live row to `ws` for
+// extend_ragged_merge_kernel. len_b, q_starts[b] and P_b are clamped, so
+// no content of a device tensor takes a load or a store out of its buffer.
+#define WS_ROW (2 + HEAD_DIM)  // floats of one (row, head, split) partial
+
+// chunk_lens[b] clamped to [0, min(max_chunk, T)]
+__device__ __forceinline__ int ragged_len(const int* chunk_lens, int b,
+                                          int max_chunk, int total_rows) {
+  return min(max(chunk_lens[b], 0), min(max_chunk, total_rows));
+}
+
+// q_starts[b] clamped to [0, T - len_b]
+__device__ __forceinline__ int ragged_start(const int* q_starts, int b,
+                                            int len_b, int total_rows) {
+  return min(max(q_starts[b], 0), total_rows - len_b);
+}
+
+// first float of the partial of row r (0..63) of q-tile `tile` of (b, h)
+// = bh, split `split` of `num_splits`; `tiles` = ceil(max_chunk / 64)
+__device__ __forceinline__ long ragged_ws_off(int bh, int tiles, int tile,
+                                              int r, int num_splits,
+                                              int split) {
+  return ((((long)bh * tiles + tile) * QT + r) * num_splits + split) * WS_ROW;
+}
+
+template <bool KV_FP8, bool HAS_PREFIX, bool RAGGED = false>
 __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
     bf16* __restrict__ out,            // [T, Hq, 128]
     const bf16* __restrict__ q,        // [T, Hq, 128]
@@ -77,21 +111,41 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
     const int num_q_heads,
     const int num_kv_heads,
     const int max_seq,
-    const float scale) {
+    const float scale,
+    const int* __restrict__ q_starts,    // [B], RAGGED only
+    const int* __restrict__ chunk_lens,  // [B], RAGGED only
+    float* __restrict__ ws,              // partials, RAGGED with splits > 1
+    const int total_rows) {              // T, RAGGED only
+  static_assert(HAS_PREFIX || !RAGGED, "RAGGED implies HAS_PREFIX");
   const int bh = blockIdx.x;           // b * Hq + h
   const int b = bh / num_q_heads;
   const int h = bh % num_q_heads;
   const int kvh = h / (num_q_heads / num_kv_heads);
   const int qt0 = blockIdx.y * QT;     // first query position of the tile
-  if (qt0 >= S) return;
+  // query rows of sequence b (S is their static bound when RAGGED) and
+  // the first of them in q/out
+  int S_b = S;
+  int row0 = b * S;
+  if constexpr (RAGGED) {
+    S_b = ragged_len(chunk_lens, b, S, total_rows);
+    row0 = ragged_start(q_starts, b, S_b, total_rows);
+  }
+  if (qt0 >= S_b) return;
 
   // first absolute position of the chunk, and rows of the slab that are
   // live (prefix + chunk); rows at or past kv_len may hold anything
   int q_pos0 = 0;
-  int kv_len = S;
+  int kv_len = S_b;
   if constexpr (HAS_PREFIX) {
     q_pos0 = min(max(prefix_lens[b], 0), max_seq);
-    kv_len = min(q_pos0 + S, max_seq);
+    kv_len = min(q_pos0 + S_b, max_seq);
+  }
+  // this workgroup's share of the kv tiles: all of them unless RAGGED
+  int kt_first = 0;
+  int kt_step = KT_POS;
+  if constexpr (RAGGED) {
+    kt_first = blockIdx.z * KT_POS;
+    kt_step = gridDim.z * KT_POS;
   }
 
   const int lane = threadIdx.x & (WAVE_SIZE - 1);
@@ -116,13 +170,13 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
   // --- persistent Q fragments for this wave's 16 rows ---
   // A-frag: lane row = q-row (l%16), k = head-dim 8·(l/16)+i, 4 subtiles
   const int my_q = qt0 + 16 * wave + (lane % 16);  // global q position
-  const bool q_live = my_q < S;
+  const bool q_live = my_q < S_b;
   bf16x8_frag q_frag[4];
   {
     const int col0 = 8 * (lane / 16);
     if (q_live) {
       const short* qrow = reinterpret_cast<const short*>(
-          q + ((long)(b * S + my_q) * num_q_heads + h) * HEAD_DIM);
+          q + ((long)(row0 + my_q) * num_q_heads + h) * HEAD_DIM);
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) {
         q_frag[kk] =
@@ -154,7 +208,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
   // causal upper bound of this q-tile's sweep
   const int kv_end = min(q_pos0 + qt0 + QT, kv_len);
 
-  for (int kt0 = 0; kt0 < kv_end; kt0 += KT_POS) {
+  for (int kt0 = kt_first; kt0 < kv_end; kt0 += kt_step) {
     const int kn = min(KT_POS, kv_len - kt0);
 
     // --- stage V tile transposed (cooperative, all waves): each
@@ -240,7 +294,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
         const int qr = qt0 + 16 * wave + (lane >> 4) * 4 + i;
         const int kp = kt0 + 16 * nt + (lane & 15);
         float v = s_frag[nt][i] * scale;
-        if (kp > q_pos0 + qr || kp >= kn + kt0 || qr >= S) v = -INFINITY;
+        if (kp > q_pos0 + qr || kp >= kn + kt0 || qr >= S_b) v = -INFINITY;
         s_frag[nt][i] = v;
         tile_max[i] = fmaxf(tile_max[i], v);
       }
@@ -326,6 +380,28 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
     __syncthreads();  // done with V before the next tile restages
   }
 
+  // --- split sweep: the unnormalised partial of every live row; a split
+  // that met no tile stores m = -inf, s = 0, o = 0 ---
+  if constexpr (RAGGED) {
+    if (gridDim.z > 1) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int r = 16 * wave + (lane >> 4) * 4 + i;
+        if (qt0 + r >= S_b) continue;
+        float* wrow = ws + ragged_ws_off(bh, gridDim.y, blockIdx.y, r,
+                                         gridDim.z, blockIdx.z);
+        if ((lane & 15) == 0) {
+          wrow[0] = m_run[i];
+          wrow[1] = s_run[i];
+        }
+#pragma unroll
+        for (int n = 0; n < 8; ++n)
+          wrow[2 + 16 * n + (lane & 15)] = o_acc[n][i];
+      }
+      return;
+    }
+  }
+
   // --- write O / s normalization: element (reg i, dim-tile n):
   // q-row = qt0 + 16·wave + (lane>>4)·4 + i, dim = 16·n + (lane&15) ---
 #pragma unroll
@@ -333,12 +409,62 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int qr = qt0 + 16 * wave + (lane >> 4) * 4 + i;
-      if (qr >= S) continue;
+      if (qr >= S_b) continue;
       const float inv = s_run[i] > 0.0f ? 1.0f / s_run[i] : 0.0f;
-      out[((long)(b * S + qr) * num_q_heads + h) * HEAD_DIM + 16 * n +
+      out[((long)(row0 + qr) * num_q_heads + h) * HEAD_DIM + 16 * n +
           (lane & 15)] = f2bf(o_acc[n][i] * inv);
     }
   }
+}
+
+// Merge of the split sweep: out row = sum_s exp(m_s - m) o_s / sum_s
+// exp(m_s - m) s_s with m = max_s m_s. Grid (B·Hq, ceil(max_chunk/64), 16):
+// a wave per row (4 rows per workgroup), a lane per dim pair; the m_s are
+// read a lane each and max-reduced, the partials of the splits are
+// independent loads. Splits with m = -inf met no visible key and are
+// skipped; a row all of whose splits are empty is written as zeros. Lengths
+// and starts are clamped exactly as in the attention kernel, so the same
+// rows are read as were written.
+#define MERGE_ROWS 4  // rows (= waves) per merge workgroup
+__global__ __launch_bounds__(64 * MERGE_ROWS) void extend_ragged_merge_kernel(
+    bf16* __restrict__ out,              // [T, Hq, 128]
+    const float* __restrict__ ws,
+    const int* __restrict__ q_starts,    // [B]
+    const int* __restrict__ chunk_lens,  // [B]
+    const int max_chunk,
+    const int num_q_heads,
+    const int num_splits,
+    const int total_rows) {
+  const int bh = blockIdx.x;
+  const int b = bh / num_q_heads;
+  const int h = bh % num_q_heads;
+  const int len_b = ragged_len(chunk_lens, b, max_chunk, total_rows);
+  const int row0 = ragged_start(q_starts, b, len_b, total_rows);
+  const int lane = threadIdx.x & (WAVE_SIZE - 1);
+  const int r = MERGE_ROWS * blockIdx.z + threadIdx.x / WAVE_SIZE;  // 0..63
+  const int qr = blockIdx.y * QT + r;
+  if (qr >= len_b) return;
+  const float* wrow =
+      ws + ragged_ws_off(bh, gridDim.y, blockIdx.y, r, num_splits, 0);
+  float m = -INFINITY;
+  for (int s = lane; s < num_splits; s += WAVE_SIZE)
+    m = fmaxf(m, wrow[s * WS_ROW]);
+  m = wave_reduce_max(m);
+  float sum = 0.0f, o0 = 0.0f, o1 = 0.0f;
+#pragma unroll 4
+  for (int s = 0; s < num_splits; ++s) {
+    const float* wsp = wrow + s * WS_ROW;
+    const float m_s = wsp[0];
+    const float f = (m_s == -INFINITY) ? 0.0f : __expf(m_s - m);
+    const float2 o = *reinterpret_cast<const float2*>(wsp + 2 + 2 * lane);
+    sum = fmaf(wsp[1], f, sum);
+    o0 = fmaf(o.x, f, o0);
+    o1 = fmaf(o.y, f, o1);
+  }
+  const float inv = sum > 0.0f ? 1.0f / sum : 0.0f;
+  bf16x2* orow = reinterpret_cast<bf16x2*>(
+      out + ((long)(row0 + qr) * num_q_heads + h) * HEAD_DIM);
+  orow[lane] = bf16x2{f2bf(o0 * inv), f2bf(o1 * inv)};
 }
 
 extern "C" void launch_prefill_attn_ex(
@@ -366,12 +492,14 @@ static void launch_prefill_kernel(
     hipLaunchKernelGGL((prefill_attn_kernel<true, HAS_PREFIX>), grid, block,
                        0, stream, (bf16*)out, (const bf16*)q, k_cache,
                        v_cache, prefix_lens, batch, rows, num_q_heads,
-                       num_kv_heads, max_seq, scale);
+                       num_kv_heads, max_seq, scale, nullptr, nullptr,
+                       nullptr, 0);
   } else {
     hipLaunchKernelGGL((prefill_attn_kernel<false, HAS_PREFIX>), grid, block,
                        0, stream, (bf16*)out, (const bf16*)q, k_cache,
                        v_cache, prefix_lens, batch, rows, num_q_heads,
-                       num_kv_heads, max_seq, scale);
+                       num_kv_heads, max_seq, scale, nullptr, nullptr,
+                       nullptr, 0);
   }
 }
 
@@ -394,4 +522,56 @@ extern "C" void launch_extend_attn(
   launch_prefill_kernel<true>(out, q, k_cache, v_cache, prefix_lens, batch,
                               chunk, num_q_heads, num_kv_heads, max_seq,
                               scale, kv_fp8, stream);
+}
+
+// Split count of the ragged extend launch from static shapes only (the
+// lengths live on the device). The kernel is resident at 3 waves/SIMD, i.e.
+// 3 workgroups per CU or 768 on 256 CUs: once the q-tiles alone fill those
+// slots the sweep is not split. Below that each workgroup walks its tiles
+// alone at ~6 us per tile and splitting pays until the launch has about
+// 2048 workgroups (measured, profiles/ragged_extend_ab.json: 8 splits at
+// 256 q-tile workgroups, 16 at 128, still gaining at 24 for 32), with at
+// most RAGGED_MAX_SPLITS, the largest count measured, and never more than
+// pairs of tiles in max_seq. The workspace needs no cap of its own: base x
+// splits <= 2048 bounds it at 2048 x 64 x 130 floats = 68 MB.
+#define RAGGED_FILL_WGS 768
+#define RAGGED_SPLIT_WGS 2048
+#define RAGGED_MAX_SPLITS 24
+extern "C" int extend_attn_ragged_num_splits(int batch, int num_q_heads,
+                                             int max_chunk, int max_seq) {
+  const long base = (long)batch * num_q_heads * ((max_chunk + QT - 1) / QT);
+  if (base < 1 || base >= RAGGED_FILL_WGS) return 1;
+  int splits = (int)(RAGGED_SPLIT_WGS / base);
+  if (splits > RAGGED_MAX_SPLITS) splits = RAGGED_MAX_SPLITS;
+  const int max_useful = (max_seq + 2 * KT_POS - 1) / (2 * KT_POS);
+  if (splits > max_useful) splits = max_useful;
+  return splits < 1 ? 1 : splits;
+}
+
+// Ragged chunked prefill: sequence b owns chunk_lens[b] <= max_chunk packed
+// rows of q/out from q_starts[b]; grid = (B·Hq, ceil(max_chunk/64),
+// num_splits), then the merge when the sweep was split. `ws` holds
+// B·Hq·ceil(max_chunk/64)·64·num_splits·(2+128) floats and may be null when
+// num_splits == 1. Nothing is read back: graph-capturable.
+extern "C" void launch_extend_attn_ragged(
+    void* out, void* ws, const void* q, const void* k_cache,
+    const void* v_cache, const int* prefix_lens, const int* q_starts,
+    const int* chunk_lens, int batch, int total_rows, int max_chunk,
+    int num_q_heads, int num_kv_heads, int max_seq, int num_splits,
+    float scale, int kv_fp8, hipStream_t stream) {
+  const auto kernel = kv_fp8 ? prefill_attn_kernel<true, true, true>
+                             : prefill_attn_kernel<false, true, true>;
+  const dim3 grid(batch * num_q_heads, (max_chunk + QT - 1) / QT, num_splits);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, (bf16*)out,
+                     (const bf16*)q, k_cache, v_cache, prefix_lens, batch,
+                     max_chunk, num_q_heads, num_kv_heads, max_seq, scale,
+                     q_starts, chunk_lens, (float*)ws, total_rows);
+  if (num_splits > 1) {
+    hipLaunchKernelGGL(extend_ragged_merge_kernel,
+                       dim3(grid.x, grid.y, QT / MERGE_ROWS),
+                       dim3(64 * MERGE_ROWS), 0, stream, (bf16*)out,
+                       (const float*)ws,
+                       q_starts, chunk_lens, max_chunk, num_q_heads,
+                       num_splits, total_rows);
+  }
 }
