@@ -21,6 +21,7 @@ from typing import List, Optional
 import torch
 
 from .. import ops
+from .paged_kv import BlockAllocator, blocks_for, full_blocks
 
 
 @dataclass
@@ -120,7 +121,18 @@ class _DecoderLayer:
 
 
 class LlamaDecodeModel:
-    """Decode-only engine with a contiguous KV cache [B, S, Hk, D]."""
+    """Llama decode engine (plus prefill and chunked prefill) over a
+    per-layer KV cache in one of two layouts:
+
+    * kv_layout="contiguous" (default): a head-major slab
+      [max_batch, Hk, max_seq, D] per layer.
+    * kv_layout="paged": a pool [num_gpu_blocks, Hk, block_size, D] per layer
+      and one block table [max_batch, max_seq / block_size] shared by all
+      layers (vLLM's num_gpu_blocks x block_size layout). `num_gpu_blocks`
+      defaults to max_batch * max_seq / block_size, the slab's bytes; a
+      smaller pool holds many short sequences. Decode path only: the
+      prefill-family methods raise NotImplementedError.
+    """
 
     def __init__(
         self,
@@ -131,8 +143,16 @@ class LlamaDecodeModel:
         seed: int = 0,
         kv_dtype: str = "bf16",
         weights_dtype: str = "bf16",
+        kv_layout: str = "contiguous",
+        block_size: int = 16,
+        num_gpu_blocks: Optional[int] = None,
     ):
         self.cfg = cfg
+        if kv_layout not in ("contiguous", "paged"):
+            raise ValueError(
+                f"kv_layout must be contiguous|paged, got {kv_layout}")
+        self.kv_layout = kv_layout
+        self.paged = kv_layout == "paged"
         self.device = torch.device(device)
         self.dtype = torch.bfloat16
         # fp8 weights: per-tensor e4m3 quantization, GEMMs via
@@ -179,6 +199,13 @@ class LlamaDecodeModel:
             self.lm_head_q = _quantize_fp8(self.lm_head)
             self.lm_head = None
 
+        self.context_lens = torch.zeros(
+            max_batch, dtype=torch.int32, device=self.device
+        )
+        self.scale = 1.0 / math.sqrt(cfg.head_dim)
+        if self.paged:
+            self._init_paged(block_size, num_gpu_blocks, seed)
+            return
         # Head-major contiguous KV cache per layer: [B, Hk, S, D] — each
         # (sequence, kv-head) is one sequential HBM stream for the
         # attention kernel's tile staging (docs/mi355x-kernels.md)
@@ -190,13 +217,123 @@ class LlamaDecodeModel:
             for _ in range(cfg.num_layers)
         ]
         self.v_cache = [torch.zeros_like(self.k_cache[0]) for _ in range(cfg.num_layers)]
-        self.context_lens = torch.zeros(
-            max_batch, dtype=torch.int32, device=self.device
-        )
-        self.scale = 1.0 / math.sqrt(cfg.head_dim)
 
-    def reset(self, batch: int, context_len: int) -> None:
-        """Random-fill KV up to context_len for `batch` sequences."""
+    # --- paged KV cache ---
+
+    def _init_paged(self, block_size, num_gpu_blocks, seed) -> None:
+        cfg = self.cfg
+        if block_size not in (16, 32, 64):
+            raise ValueError(f"block_size must be 16|32|64, got {block_size}")
+        if self.max_seq % block_size:
+            raise ValueError(
+                f"max_seq={self.max_seq} must be a multiple of "
+                f"block_size={block_size}")
+        self.block_size = block_size
+        self.max_blocks = self.max_seq // block_size
+        if num_gpu_blocks is None:
+            num_gpu_blocks = self.max_batch * self.max_blocks
+        if num_gpu_blocks < 1:
+            raise ValueError(f"num_gpu_blocks must be >= 1")
+        self.num_gpu_blocks = num_gpu_blocks
+        self.allocator = BlockAllocator(num_gpu_blocks, seed=seed)
+        self.k_pages = [
+            torch.zeros(
+                num_gpu_blocks, cfg.num_kv_heads, block_size, cfg.head_dim,
+                device=self.device, dtype=self.cache_dtype,
+            )
+            for _ in range(cfg.num_layers)
+        ]
+        self.v_pages = [
+            torch.zeros_like(self.k_pages[0]) for _ in range(cfg.num_layers)
+        ]
+        # One table for all layers. Its storage never changes: reset writes
+        # into it in place, so a captured graph keeps seeing it. Unreserved
+        # entries hold -1.
+        self.block_tables = torch.full(
+            (self.max_batch, self.max_blocks), -1, dtype=torch.int32,
+            device=self.device,
+        )
+
+    def _reset_paged(self, batch, context_len, headroom, shared_prefix):
+        bs = self.block_size
+        if batch > self.max_batch:
+            raise ValueError(f"batch={batch}, max_batch={self.max_batch}")
+        reserve = (
+            self.max_seq if headroom is None else context_len + headroom
+        )
+        if context_len > reserve or reserve > self.max_seq:
+            raise ValueError(
+                f"context {context_len}, reservation {reserve}, "
+                f"max_seq={self.max_seq}")
+        if shared_prefix < 0 or shared_prefix > context_len:
+            raise ValueError(
+                f"shared_prefix={shared_prefix} outside the context "
+                f"{context_len}")
+        per_seq = blocks_for(reserve, bs)
+        shared = full_blocks(shared_prefix, bs)
+        alloc = self.allocator
+        alloc.reset()  # frees everything
+        need = per_seq * batch - shared * max(batch - 1, 0)
+        if need > alloc.num_free:
+            raise RuntimeError(
+                f"paged KV pool too small: {batch} sequences x {per_seq} "
+                f"blocks ({shared} shared) need {need} blocks, "
+                f"{alloc.num_free} free of {self.num_gpu_blocks}")
+        tables = torch.full(
+            (self.max_batch, self.max_blocks), -1, dtype=torch.int32)
+        for b in range(batch):
+            if b and shared:
+                alloc.share(0, b, shared)
+                alloc.allocate(b, per_seq - shared)
+            else:
+                alloc.allocate(b, per_seq)
+            tables[b, :per_seq] = torch.tensor(
+                alloc.blocks(b), dtype=torch.int32)
+        self.block_tables.copy_(tables)  # in place
+        self.context_lens.zero_()
+        self.context_lens[:batch] = context_len
+        # random-fill the pages that hold live rows
+        live = blocks_for(context_len, bs)
+        if batch == 0 or live == 0:
+            return
+        ids = torch.unique(tables[:batch, :live].reshape(-1)).long().to(
+            self.device)
+        shape = (ids.numel(),) + tuple(self.k_pages[0].shape[1:])
+        for layer in range(self.cfg.num_layers):
+            for pool in (self.k_pages, self.v_pages):
+                fill = torch.randn(
+                    shape, device=self.device, dtype=torch.bfloat16
+                ).to(self.cache_dtype)
+                ops._as_bytes(pool[layer])[ids] = ops._as_bytes(fill)
+
+    def _decode_only(self) -> None:
+        if self.paged:
+            raise NotImplementedError("paged KV: decode path only")
+
+    def reset(
+        self,
+        batch: int,
+        context_len: int,
+        headroom: Optional[int] = None,
+        shared_prefix: int = 0,
+    ) -> None:
+        """Random-fill KV up to context_len for `batch` sequences.
+
+        Paged layout: frees every block, then reserves
+        ceil((context_len + headroom) / block_size) blocks per sequence
+        (`headroom=None`: up to max_seq), handed out in a seeded, shuffled
+        order so that sequences are scattered over the pool. With
+        `shared_prefix > 0` the first shared_prefix // block_size blocks of
+        every sequence are the same physical blocks (the prefix-cache-hit
+        layout). Writes the block table in place and raises RuntimeError
+        when the pool cannot cover the reservation. `headroom` and
+        `shared_prefix` have no meaning for the contiguous layout."""
+        if self.paged:
+            self._reset_paged(batch, context_len, headroom, shared_prefix)
+            return
+        if headroom is not None or shared_prefix:
+            raise ValueError(
+                "headroom and shared_prefix need kv_layout=\"paged\"")
         self.context_lens.zero_()
         self.context_lens[:batch] = context_len
         for layer in range(self.cfg.num_layers):
@@ -238,7 +375,15 @@ class LlamaDecodeModel:
     def decode_step(self, token_ids: torch.Tensor) -> torch.Tensor:
         """One decode iteration for `B = len(token_ids)` sequences.
         Appends each sequence's new KV at position context_lens[b] and
-        returns logits [B, vocab]."""
+        returns logits [B, vocab].
+
+        Paged layout: the append and the attention go through the block
+        table on the device; the step does no host work and no allocation,
+        so it is graph-capturable as it is. Stepping a sequence past the
+        blocks that `reset` reserved for it is the caller's error: by the
+        kernels' addressing rules (an append without a page is skipped, an
+        unreserved table entry is clamped into the pool) it produces wrong
+        numbers and no bad access."""
         cfg = self.cfg
         B = token_ids.shape[0]
         positions = self.context_lens[:B].clone()
@@ -258,14 +403,27 @@ class LlamaDecodeModel:
 
             qkv = self._linear(h, layer, "wqkv")
             # fused: RoPE on the strided qkv row + KV-cache append
-            q = ops.rope_append_kv(
-                qkv, self.k_cache[li][:B], self.v_cache[li][:B],
-                positions, cfg.num_q_heads, cfg.num_kv_heads, cfg.rope_theta,
-            )
-
-            attn = ops.gqa_decode_attn(
-                q, self.k_cache[li][:B], self.v_cache[li][:B], ctx, self.scale
-            )
+            if self.paged:
+                tables = self.block_tables[:B]
+                q = ops.rope_append_kv_paged(
+                    qkv, self.k_pages[li], self.v_pages[li], tables,
+                    positions, cfg.num_q_heads, cfg.num_kv_heads,
+                    cfg.rope_theta,
+                )
+                attn = ops.paged_decode_attn(
+                    q, self.k_pages[li], self.v_pages[li], tables, ctx,
+                    self.scale,
+                )
+            else:
+                q = ops.rope_append_kv(
+                    qkv, self.k_cache[li][:B], self.v_cache[li][:B],
+                    positions, cfg.num_q_heads, cfg.num_kv_heads,
+                    cfg.rope_theta,
+                )
+                attn = ops.gqa_decode_attn(
+                    q, self.k_cache[li][:B], self.v_cache[li][:B], ctx,
+                    self.scale,
+                )
             x = self._linear(attn.reshape(B, cfg.q_size), layer, "wo")
 
             h2 = ops.rmsnorm(x, layer.post_attn_norm, residual, cfg.rms_eps)
@@ -298,6 +456,7 @@ class LlamaDecodeModel:
         decode path. RMSNorm/RoPE/SwiGLU reuse the HIP kernels (they are
         row-shaped and batch-size-agnostic).
         """
+        self._decode_only()
         if chunk_size is not None:
             return self._prefill_chunked(token_ids, int(chunk_size))
         cfg = self.cfg
@@ -423,6 +582,7 @@ class LlamaDecodeModel:
         advances by C. Returns the chunk's last-position logits
         [B, vocab]. Everything per-sequence stays on the device; the
         caller keeps context_lens[b] + C within max_seq."""
+        self._decode_only()
         return self._chunk_step(None, token_ids)
 
     @torch.no_grad()
@@ -436,6 +596,7 @@ class LlamaDecodeModel:
         weights); only attention splits by row range. Returns logits
         [Bd+Bp, vocab]: the decode rows, then each chunk's last position.
         context_lens advances by 1 and by C respectively."""
+        self._decode_only()
         return self._chunk_step(decode_tokens, chunk_tokens)
 
     def _chunk_step(
@@ -562,6 +723,7 @@ class LlamaDecodeModel:
         context_lens and cache rows stay as they are). context_lens advances
         by 1 and by chunk_lens respectively; the caller keeps
         context_lens[b] + chunk_lens[b] within max_seq."""
+        self._decode_only()
         if self.weights_dtype != "bf16":
             raise NotImplementedError(
                 "chunked prefill with fp8 weights is not implemented"

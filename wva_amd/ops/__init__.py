@@ -132,6 +132,60 @@ def gqa_decode_attn_ref(
     return out
 
 
+def _as_bytes(t: torch.Tensor) -> torch.Tensor:
+    """e4m3 tensors are indexed as bytes (a view of the same storage)."""
+    return t.view(torch.uint8) if t.dtype == torch.float8_e4m3fn else t
+
+
+def gather_pages(
+    pages: torch.Tensor, block_tables: torch.Tensor, context_lens: torch.Tensor
+) -> torch.Tensor:
+    """Materialise a paged pool [num_blocks, Hk, block_size, D] as the
+    contiguous head-major cache [B, Hk, max_blocks * block_size, D] that the
+    paged kernels see, by their addressing rules: the effective context is
+    min(context_lens[b], max_blocks * block_size), only the table entries
+    below ceil(ctx / block_size) are looked at, and an id is clamped into
+    [0, num_blocks - 1]. Rows of pages that are not looked at stay 0."""
+    num_blocks, Hk, bs, D = pages.shape
+    B, max_blocks = block_tables.shape
+    out = torch.zeros(
+        B, Hk, max_blocks * bs, D, dtype=pages.dtype, device=pages.device
+    )
+    src, dst = _as_bytes(pages), _as_bytes(out)
+    for b in range(B):
+        ctx = min(int(context_lens[b]), max_blocks * bs)
+        n = (ctx + bs - 1) // bs
+        if n <= 0:
+            continue
+        ids = block_tables[b, :n].long().clamp(0, num_blocks - 1)
+        dst[b, :, : n * bs] = (
+            src[ids].permute(1, 0, 2, 3).reshape(Hk, n * bs, D)
+        )
+    return out
+
+
+def paged_decode_attn_ref(
+    q: torch.Tensor,
+    k_pages: torch.Tensor,
+    v_pages: torch.Tensor,
+    block_tables: torch.Tensor,
+    context_lens: torch.Tensor,
+    scale: float,
+):
+    """fp32 reference of paged decode attention: gather each sequence's
+    pages into a contiguous cache (gather_pages) and run
+    gqa_decode_attn_ref on it."""
+    max_ctx = block_tables.shape[1] * k_pages.shape[2]
+    ctx = context_lens.clamp(min=0, max=max_ctx)
+    return gqa_decode_attn_ref(
+        q,
+        gather_pages(k_pages, block_tables, ctx),
+        gather_pages(v_pages, block_tables, ctx),
+        ctx,
+        scale,
+    )
+
+
 def extend_attn_ref(
     q: torch.Tensor,
     k_cache: torch.Tensor,
@@ -335,7 +389,21 @@ def rope_append_kv(
             num_q_heads, num_kv_heads, theta,
         )
     B = qkv.shape[0]
-    D = k_cache.shape[3]
+    q, k, v = _rope_split_qkv(
+        qkv, k_cache.shape[3], positions, num_q_heads, num_kv_heads, theta
+    )
+    # head-major cache [B, Hk, S, D]
+    idx = torch.arange(B)
+    k_cache[idx, :, positions.long()] = k.to(k_cache.dtype)
+    v_cache[idx, :, positions.long()] = v.to(v_cache.dtype)
+    return q
+
+
+def _rope_split_qkv(qkv, D, positions, num_q_heads, num_kv_heads, theta):
+    """CPU reference of the append ops' rotation: the qkv row split into
+    RoPE'd q [B, Hq, D] and k [B, Hk, D] (rounded to qkv's dtype) and the
+    raw v [B, Hk, D]."""
+    B = qkv.shape[0]
     q = qkv[:, : num_q_heads * D].reshape(B, num_q_heads, D).contiguous()
     k = (
         qkv[:, num_q_heads * D : (num_q_heads + num_kv_heads) * D]
@@ -346,10 +414,45 @@ def rope_append_kv(
     qr, kr = rope_ref(q, k, positions, theta)
     q.copy_(qr.to(q.dtype))
     k.copy_(kr.to(k.dtype))
-    # head-major cache [B, Hk, S, D]
-    idx = torch.arange(B)
-    k_cache[idx, :, positions.long()] = k.to(k_cache.dtype)
-    v_cache[idx, :, positions.long()] = v.to(v_cache.dtype)
+    return q, k, v
+
+
+def rope_append_kv_paged(
+    qkv: torch.Tensor,
+    k_pages: torch.Tensor,
+    v_pages: torch.Tensor,
+    block_tables: torch.Tensor,
+    positions: torch.Tensor,
+    num_q_heads: int,
+    num_kv_heads: int,
+    theta: float = 500000.0,
+) -> torch.Tensor:
+    """rope_append_kv into a paged pool [num_blocks, Hk, block_size, D]:
+    sequence b's K/V row goes to page block_tables[b, pos // block_size],
+    row pos % block_size. If pos // block_size is past the table or the
+    entry is outside [0, num_blocks), that sequence's K/V stores are
+    skipped; q is produced all the same. block_tables [B, max_blocks] and
+    positions [B] are read on the device (graph-capturable). Returns
+    contiguous q [B, Hq, D]."""
+    if qkv.is_cuda:
+        return _require_ext().rope_append_kv_paged(
+            qkv, k_pages, v_pages, block_tables.to(torch.int32),
+            positions.to(torch.int32), num_q_heads, num_kv_heads, theta,
+        )
+    num_blocks, _, bs, D = k_pages.shape
+    max_blocks = block_tables.shape[1]
+    q, k, v = _rope_split_qkv(
+        qkv, D, positions, num_q_heads, num_kv_heads, theta
+    )
+    pos = positions.long()
+    entry = torch.div(pos, bs, rounding_mode="floor")
+    in_table = (pos >= 0) & (entry < max_blocks)
+    seq = torch.arange(qkv.shape[0])
+    ids = block_tables.long()[seq, entry.clamp(0, max_blocks - 1)]
+    ok = in_table & (ids >= 0) & (ids < num_blocks)
+    ids, rows = ids[ok], (pos % bs)[ok]
+    _as_bytes(k_pages)[ids, :, rows] = _as_bytes(k.to(k_pages.dtype))[ok]
+    _as_bytes(v_pages)[ids, :, rows] = _as_bytes(v.to(v_pages.dtype))[ok]
     return q
 
 
@@ -387,6 +490,55 @@ def gqa_decode_num_splits(batch: int, num_kv_heads: int, max_seq: int) -> int:
     return int(
         _require_ext().gqa_decode_attn_splits(batch, num_kv_heads, max_seq)
     )
+
+
+def paged_decode_num_splits(
+    batch: int, num_kv_heads: int, max_blocks: int, block_size: int
+) -> int:
+    """Split-KV factor paged_decode_attn picks for block tables of
+    `max_blocks` entries: that of a contiguous cache of max_blocks *
+    block_size rows."""
+    return gqa_decode_num_splits(batch, num_kv_heads, max_blocks * block_size)
+
+
+def paged_decode_attn(
+    q: torch.Tensor,
+    k_pages: torch.Tensor,
+    v_pages: torch.Tensor,
+    block_tables: torch.Tensor,
+    context_lens: torch.Tensor,
+    scale: Optional[float] = None,
+    num_splits: Optional[int] = None,
+    variant: str = "auto",
+) -> torch.Tensor:
+    """GQA decode attention over a paged KV pool. k_pages / v_pages are
+    [num_blocks, Hk, block_size, 128] (bf16 or float8_e4m3fn, block_size
+    16, 32 or 64); block_tables [B, max_blocks] int32 maps sequence b's
+    block i to a physical page and context_lens [B] int32 gives its length.
+    Both are read on the device only (no host sync, graph-capturable).
+
+    The effective context is min(context_lens[b], max_blocks * block_size);
+    table entries at or past ceil(ctx / block_size) are never looked at and
+    an id outside [0, num_blocks) is clamped into the pool, so a corrupt
+    table gives wrong numbers, never an out-of-bounds access. `num_splits`
+    forces the split-KV factor; None asks paged_decode_num_splits.
+    `variant` pins "v4" or "v5"; "auto" applies the rule measured on the
+    contiguous layout."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    if q.is_cuda:
+        if num_splits is None:
+            num_splits = paged_decode_num_splits(
+                q.shape[0], k_pages.shape[1], block_tables.shape[1],
+                k_pages.shape[2],
+            )
+        return _require_ext().paged_decode_attn(
+            q, k_pages, v_pages, block_tables.to(torch.int32),
+            context_lens.to(torch.int32), scale, num_splits, variant,
+        )
+    return paged_decode_attn_ref(
+        q, k_pages, v_pages, block_tables, context_lens, scale
+    ).to(q.dtype)
 
 
 def moe_route(router_logits: torch.Tensor, top_k: int):

@@ -11,7 +11,11 @@
 //       LDS, VALU PV — best for G < 8 with split-KV
 //   v5  v4 + MFMA PV (P cast to bf16, corr/s broadcast via LDS) — best
 //       for G = 8 or unsplit grids
-// plus the split-KV merge kernel. The Q-fragment build, the online-softmax
+// plus the split-KV merge kernel. Both kernels also run over a paged pool
+// [num_blocks, Hk, block_size, 128] addressed through block tables (PAGED
+// template parameter): only the K row address, the staged V row's source
+// and the clamp for positions past the context differ, see "Paged pool
+// addressing" below. The Q-fragment build, the online-softmax
 // step and the workspace addressing exist once, as __device__ helpers used
 // by both kernels. V staging and the MFMA score tile are written out in
 // each kernel: as helpers they compiled to different fp8 code that
@@ -170,29 +174,98 @@ __device__ __forceinline__ SoftmaxStep online_softmax_step(
 }
 
 // ---------------------------------------------------------------------------
+// Paged pool addressing (PAGED instantiations only). k_pages / v_pages are
+// [num_blocks, Hk, block_size, 128] with block_size in {16, 32, 64}, the
+// divisors of TILE that are multiples of 16: one (page, kv-head) is a
+// contiguous run of block_size rows, and each aligned group of 16 positions
+// (a wave's 16 score rows, a wave's staged V rows of one pass) lies inside
+// one page. block_tables is [B, max_blocks] int32; entry i of row b is the
+// physical page of sequence b's positions i·block_size .. (i+1)·block_size−1.
+//
+// Rules that keep every access inside the pool whatever the tables hold:
+//   * the effective context is min(context_lens[b], max_blocks·block_size);
+//   * a position at or past the context is clamped to ctx − 1 BEFORE the
+//     table lookup, so table entries at index >= ceil(ctx / block_size) are
+//     never dereferenced;
+//   * a physical id read from the table is clamped into [0, num_blocks − 1]
+//     before it forms an address.
+// A corrupt table therefore yields wrong numbers, never an out-of-bounds
+// access.
+// ---------------------------------------------------------------------------
+
+// Physical page ids of a tile's four 16-position groups, fetched once per
+// tile through wave-uniform indices (scalar loads), never per element.
+struct TilePages {
+  int id[4];
+
+  // `group` is wave-uniform; a select chain keeps id[] in registers (a
+  // runtime-indexed array would go to scratch).
+  __device__ __forceinline__ int pick(int group) const {
+    return group == 0 ? id[0] : group == 1 ? id[1] : group == 2 ? id[2] : id[3];
+  }
+};
+
+// `table_row` = block_tables + b·max_blocks; t0 < ctx, ctx >= 1 already the
+// effective context. Group g covers positions t0 + 16g .. t0 + 16g + 15; a
+// group that starts at or past ctx takes the page of position ctx − 1, which
+// is where its clamped rows read.
+__device__ __forceinline__ TilePages load_tile_pages(
+    const int* __restrict__ table_row, int t0, int ctx, int block_shift,
+    int num_blocks) {
+  const int last_block = (ctx - 1) >> block_shift;  // last entry ever read
+  TilePages pages;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const int entry = min((t0 + 16 * g) >> block_shift, last_block);
+    const int id = table_row[entry];
+    pages.id[g] = min(max(id, 0), num_blocks - 1);  // never leaves the pool
+  }
+  return pages;
+}
+
+// Row of position `pos` (< ctx) in its page. `head0` points at this kv-head's
+// rows of page 0, `page_stride` = Hk·block_size·128 elements; the page
+// offset is formed in 64-bit.
+template <typename T>
+__device__ __forceinline__ const T* page_row(const T* head0,
+                                             const TilePages& pages, int group,
+                                             int pos, int block_mask,
+                                             long page_stride) {
+  return head0 + (long)pages.pick(group) * page_stride +
+         (long)(pos & block_mask) * HEAD_DIM;
+}
+
+// ---------------------------------------------------------------------------
 // v4: MFMA scores, VALU PV. Wave w owns the softmax state and the output
 // of heads w and w+4 (lane ↔ output dword); only V goes through LDS (the
 // position-major PV sweep needs the transpose LDS provides). 2 barriers
 // per tile.
 // ---------------------------------------------------------------------------
-template <bool KV_FP8>
+template <bool KV_FP8, bool PAGED>
 __global__ __launch_bounds__(256, 2) void gqa_decode_attn_v4_kernel(
     bf16* __restrict__ out,            // [B, Hq, 128]
     float* __restrict__ workspace,     // [B, Hk, G, splits, 2+128] or null
     const bf16* __restrict__ q,        // [B, Hq, 128]
-    const void* __restrict__ k_cache,  // [B, Hk, S_max, 128] bf16 or e4m3
-    const void* __restrict__ v_cache,
+    const void* __restrict__ k_cache,  // [B, Hk, S_max, 128] bf16 or e4m3;
+    const void* __restrict__ v_cache,  // PAGED: [num_blocks, Hk, bs, 128]
     const int* __restrict__ context_lens,  // [B]
     const int num_q_heads,
     const int num_kv_heads,
-    const int max_seq,
-    const float scale) {
+    const int max_seq,                 // PAGED: max_blocks · block_size
+    const float scale,
+    // PAGED only (null / 0 otherwise)
+    const int* __restrict__ block_tables,  // [B, max_blocks]
+    const int max_blocks,
+    const int block_shift,             // log2(block_size)
+    const int num_blocks) {
   const int b = blockIdx.x;
   const int kvh = blockIdx.y;
   const int split = blockIdx.z;
   const int num_splits = gridDim.z;
   const int G = num_q_heads / num_kv_heads;
-  const int ctx = context_lens[b];
+  // PAGED: effective context, see "Paged pool addressing"
+  const int ctx =
+      PAGED ? min(context_lens[b], max_seq) : context_lens[b];
 
   const int lane = threadIdx.x & (WAVE_SIZE - 1);
   const int wave = threadIdx.x / WAVE_SIZE;
@@ -222,8 +295,14 @@ __global__ __launch_bounds__(256, 2) void gqa_decode_attn_v4_kernel(
     acc[j][0] = acc[j][1] = 0.0f;
   }
 
-  // head-major cache: this (b, kvh)'s positions are contiguous
-  const long slab_off = ((long)b * num_kv_heads + kvh) * max_seq * HEAD_DIM;
+  // head-major cache: this (b, kvh)'s positions are contiguous. PAGED:
+  // k_slab / v_slab are this kv-head's rows of page 0.
+  const long slab_off =
+      PAGED ? (long)kvh << (block_shift + 7)
+            : ((long)b * num_kv_heads + kvh) * max_seq * HEAD_DIM;
+  const long page_stride = (long)num_kv_heads << (block_shift + 7);
+  const int block_mask = (1 << block_shift) - 1;
+  const int* table_row = block_tables + (long)b * max_blocks;
   const auto* k_slab =
       reinterpret_cast<const kv_elem_t<KV_FP8>*>(k_cache) + slab_off;
   const auto* v_slab =
@@ -232,6 +311,9 @@ __global__ __launch_bounds__(256, 2) void gqa_decode_attn_v4_kernel(
   // Interleave tiles across splits: split s takes tiles s, s+S, s+2S, ...
   for (int t0 = split * TILE; t0 < ctx; t0 += num_splits * TILE) {
     const int tn = min(TILE, ctx - t0);
+    TilePages pages;
+    if constexpr (PAGED)
+      pages = load_tile_pages(table_row, t0, ctx, block_shift, num_blocks);
 
     // --- stage V only; the fp8 path up-converts during staging so the
     // LDS layout and PV sweep are identical in both modes ---
@@ -242,9 +324,15 @@ __global__ __launch_bounds__(256, 2) void gqa_decode_attn_v4_kernel(
            idx += NUM_WAVES * WAVE_SIZE) {
         const int row = idx >> 4;          // 16 groups of 8 per row
         const int d8 = (idx & 15) * 8;
+        const fp8_t* v_row;
+        if constexpr (PAGED)  // a wave's 4 rows of a pass share a page
+          v_row = page_row(v_slab, pages,
+                           __builtin_amdgcn_readfirstlane(row >> 4), t0 + row,
+                           block_mask, page_stride);
+        else
+          v_row = v_src + (long)row * HEAD_DIM;
         const unsigned short* src =
-            reinterpret_cast<const unsigned short*>(
-                v_src + (long)row * HEAD_DIM + d8);
+            reinterpret_cast<const unsigned short*>(v_row + d8);
         unsigned int* dst = &v_smem[row * ROW_DW + d8 / 2];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -262,7 +350,14 @@ __global__ __launch_bounds__(256, 2) void gqa_decode_attn_v4_kernel(
            idx += NUM_WAVES * WAVE_SIZE) {
         const int row = idx >> 5;
         const int d2 = (idx & 31) * 2;
-        const uint2_t val = *reinterpret_cast<const uint2_t*>(&v_src[idx * 2]);
+        const unsigned int* src;
+        if constexpr (PAGED)  // a wave's 2 rows of a pass share a page
+          src = reinterpret_cast<const unsigned int*>(page_row(
+                    v_slab, pages, __builtin_amdgcn_readfirstlane(row >> 4),
+                    t0 + row, block_mask, page_stride)) + d2;
+        else
+          src = &v_src[idx * 2];
+        const uint2_t val = *reinterpret_cast<const uint2_t*>(src);
         *reinterpret_cast<uint2_t*>(&v_smem[row * ROW_DW + d2]) = val;
       }
     }
@@ -271,14 +366,22 @@ __global__ __launch_bounds__(256, 2) void gqa_decode_attn_v4_kernel(
     {
       const int prow = 16 * wave + (lane % 16);       // A row = position
       const int pos = t0 + prow;
-      const int pos_c = pos < max_seq ? pos : max_seq - 1;  // clamped load
+      // clamped load. PAGED clamps to the context (not the cache size)
+      // before the table lookup; the wave's 16 rows share a page.
+      const int pos_lim = PAGED ? ctx : max_seq;
+      const int pos_c = pos < pos_lim ? pos : pos_lim - 1;
+      const kv_elem_t<KV_FP8>* k_row;
+      if constexpr (PAGED)
+        k_row = page_row(k_slab, pages, __builtin_amdgcn_readfirstlane(wave),
+                         pos_c, block_mask, page_stride);
+      else
+        k_row = k_slab + (long)pos_c * HEAD_DIM;
       const int k0 = frag_k0;
       f32x4_frag sf = {0.f, 0.f, 0.f, 0.f};
       if constexpr (KV_FP8) {
         // fp8×fp8 MFMA: K bytes fed raw (8 per lane, one b64 load);
         // Q was pre-quantized with scale q_scale
-        const long* ksrc = reinterpret_cast<const long*>(
-            k_slab + (long)pos_c * HEAD_DIM);
+        const long* ksrc = reinterpret_cast<const long*>(k_row);
         const int l0 = k0 / 8;  // which 8-byte group this lane reads
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
@@ -290,8 +393,8 @@ __global__ __launch_bounds__(256, 2) void gqa_decode_attn_v4_kernel(
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
           bf16x8_frag a_frag;
-          const short* src = reinterpret_cast<const short*>(
-              k_slab + (long)pos_c * HEAD_DIM) + 32 * kk + k0;
+          const short* src =
+              reinterpret_cast<const short*>(k_row) + 32 * kk + k0;
 #pragma unroll
           for (int i = 0; i < 8; ++i) a_frag[i] = src[i];
           sf = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_frag, qf.bf[kk],
@@ -381,7 +484,7 @@ __global__ __launch_bounds__(256, 2) void gqa_decode_attn_v4_kernel(
 // p row; 3 per tile plus one before the epilogue) and LDS broadcast of
 // corr/s; softmax state stays wave-owned.
 // ---------------------------------------------------------------------------
-template <bool KV_FP8>
+template <bool KV_FP8, bool PAGED>
 __global__ __launch_bounds__(256, 2) void gqa_decode_attn_v5_kernel(
     bf16* __restrict__ out,
     float* __restrict__ workspace,
@@ -392,13 +495,19 @@ __global__ __launch_bounds__(256, 2) void gqa_decode_attn_v5_kernel(
     const int num_q_heads,
     const int num_kv_heads,
     const int max_seq,
-    const float scale) {
+    const float scale,
+    const int* __restrict__ block_tables,  // PAGED only, as in v4
+    const int max_blocks,
+    const int block_shift,
+    const int num_blocks) {
   const int b = blockIdx.x;
   const int kvh = blockIdx.y;
   const int split = blockIdx.z;
   const int num_splits = gridDim.z;
   const int G = num_q_heads / num_kv_heads;
-  const int ctx = context_lens[b];
+  // PAGED: effective context, see "Paged pool addressing"
+  const int ctx =
+      PAGED ? min(context_lens[b], max_seq) : context_lens[b];
 
   const int lane = threadIdx.x & (WAVE_SIZE - 1);
   const int wave = threadIdx.x / WAVE_SIZE;
@@ -433,7 +542,12 @@ __global__ __launch_bounds__(256, 2) void gqa_decode_attn_v5_kernel(
   f32x4_frag acc_pv[2] = {f32x4_frag{0.f, 0.f, 0.f, 0.f},
                           f32x4_frag{0.f, 0.f, 0.f, 0.f}};
 
-  const long slab_off = ((long)b * num_kv_heads + kvh) * max_seq * HEAD_DIM;
+  const long slab_off =
+      PAGED ? (long)kvh << (block_shift + 7)
+            : ((long)b * num_kv_heads + kvh) * max_seq * HEAD_DIM;
+  const long page_stride = (long)num_kv_heads << (block_shift + 7);
+  const int block_mask = (1 << block_shift) - 1;
+  const int* table_row = block_tables + (long)b * max_blocks;
   const auto* k_slab =
       reinterpret_cast<const kv_elem_t<KV_FP8>*>(k_cache) + slab_off;
   const auto* v_slab =
@@ -441,6 +555,9 @@ __global__ __launch_bounds__(256, 2) void gqa_decode_attn_v5_kernel(
 
   for (int t0 = split * TILE; t0 < ctx; t0 += num_splits * TILE) {
     const int tn = min(TILE, ctx - t0);
+    TilePages pages;
+    if constexpr (PAGED)
+      pages = load_tile_pages(table_row, t0, ctx, block_shift, num_blocks);
 
     // --- stage V only; the fp8 path up-converts during staging so the
     // LDS layout and PV sweep are identical in both modes ---
@@ -451,9 +568,15 @@ __global__ __launch_bounds__(256, 2) void gqa_decode_attn_v5_kernel(
            idx += NUM_WAVES * WAVE_SIZE) {
         const int row = idx >> 4;          // 16 groups of 8 per row
         const int d8 = (idx & 15) * 8;
+        const fp8_t* v_row;
+        if constexpr (PAGED)  // a wave's 4 rows of a pass share a page
+          v_row = page_row(v_slab, pages,
+                           __builtin_amdgcn_readfirstlane(row >> 4), t0 + row,
+                           block_mask, page_stride);
+        else
+          v_row = v_src + (long)row * HEAD_DIM;
         const unsigned short* src =
-            reinterpret_cast<const unsigned short*>(
-                v_src + (long)row * HEAD_DIM + d8);
+            reinterpret_cast<const unsigned short*>(v_row + d8);
         unsigned int* dst = &v_smem[row * ROW_DW + d8 / 2];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -471,7 +594,14 @@ __global__ __launch_bounds__(256, 2) void gqa_decode_attn_v5_kernel(
            idx += NUM_WAVES * WAVE_SIZE) {
         const int row = idx >> 5;
         const int d2 = (idx & 31) * 2;
-        const uint2_t val = *reinterpret_cast<const uint2_t*>(&v_src[idx * 2]);
+        const unsigned int* src;
+        if constexpr (PAGED)  // a wave's 2 rows of a pass share a page
+          src = reinterpret_cast<const unsigned int*>(page_row(
+                    v_slab, pages, __builtin_amdgcn_readfirstlane(row >> 4),
+                    t0 + row, block_mask, page_stride)) + d2;
+        else
+          src = &v_src[idx * 2];
+        const uint2_t val = *reinterpret_cast<const uint2_t*>(src);
         *reinterpret_cast<uint2_t*>(&v_smem[row * ROW_DW + d2]) = val;
       }
     }
@@ -480,14 +610,22 @@ __global__ __launch_bounds__(256, 2) void gqa_decode_attn_v5_kernel(
     {
       const int prow = 16 * wave + (lane % 16);       // A row = position
       const int pos = t0 + prow;
-      const int pos_c = pos < max_seq ? pos : max_seq - 1;  // clamped load
+      // clamped load. PAGED clamps to the context (not the cache size)
+      // before the table lookup; the wave's 16 rows share a page.
+      const int pos_lim = PAGED ? ctx : max_seq;
+      const int pos_c = pos < pos_lim ? pos : pos_lim - 1;
+      const kv_elem_t<KV_FP8>* k_row;
+      if constexpr (PAGED)
+        k_row = page_row(k_slab, pages, __builtin_amdgcn_readfirstlane(wave),
+                         pos_c, block_mask, page_stride);
+      else
+        k_row = k_slab + (long)pos_c * HEAD_DIM;
       const int k0 = frag_k0;
       f32x4_frag sf = {0.f, 0.f, 0.f, 0.f};
       if constexpr (KV_FP8) {
         // fp8×fp8 MFMA: K bytes fed raw (8 per lane, one b64 load);
         // Q was pre-quantized with scale q_scale
-        const long* ksrc = reinterpret_cast<const long*>(
-            k_slab + (long)pos_c * HEAD_DIM);
+        const long* ksrc = reinterpret_cast<const long*>(k_row);
         const int l0 = k0 / 8;  // which 8-byte group this lane reads
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
@@ -499,8 +637,8 @@ __global__ __launch_bounds__(256, 2) void gqa_decode_attn_v5_kernel(
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
           bf16x8_frag a_frag;
-          const short* src = reinterpret_cast<const short*>(
-              k_slab + (long)pos_c * HEAD_DIM) + 32 * kk + k0;
+          const short* src =
+              reinterpret_cast<const short*>(k_row) + 32 * kk + k0;
 #pragma unroll
           for (int i = 0; i < 8; ++i) a_frag[i] = src[i];
           sf = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_frag, qf.bf[kk],
@@ -739,14 +877,42 @@ extern "C" void launch_gqa_decode_attn(
     int num_kv_heads, int max_seq, int num_splits, float scale, int variant,
     int kv_fp8, hipStream_t stream) {
   const auto kernel =
-      variant == 5 ? (kv_fp8 ? gqa_decode_attn_v5_kernel<true>
-                             : gqa_decode_attn_v5_kernel<false>)
-                   : (kv_fp8 ? gqa_decode_attn_v4_kernel<true>
-                             : gqa_decode_attn_v4_kernel<false>);
+      variant == 5 ? (kv_fp8 ? gqa_decode_attn_v5_kernel<true, false>
+                             : gqa_decode_attn_v5_kernel<false, false>)
+                   : (kv_fp8 ? gqa_decode_attn_v4_kernel<true, false>
+                             : gqa_decode_attn_v4_kernel<false, false>);
   hipLaunchKernelGGL(kernel, dim3(batch, num_kv_heads, num_splits), dim3(256),
                      0, stream, (bf16*)out, (float*)workspace, (const bf16*)q,
                      k_cache, v_cache, context_lens, num_q_heads, num_kv_heads,
-                     max_seq, scale);
+                     max_seq, scale, (const int*)nullptr, 0, 0, 0);
+  if (num_splits > 1) {
+    hipLaunchKernelGGL(gqa_decode_attn_merge_kernel,
+                       dim3(batch, num_q_heads), dim3(64 * MERGE_WAVES), 0,
+                       stream, (bf16*)out, (const float*)workspace,
+                       num_q_heads, num_kv_heads, num_splits);
+  }
+}
+
+// The same over a paged pool: k_pages / v_pages [num_blocks, Hk, block_size,
+// 128] with block_size = 1 << block_shift in {16, 32, 64}, block_tables
+// [batch, max_blocks]. Same grid, workspace and merge as the contiguous
+// launch; the caller picks num_splits.
+extern "C" void launch_paged_decode_attn(
+    void* out, void* workspace, const void* q, const void* k_pages,
+    const void* v_pages, const int* block_tables, const int* context_lens,
+    int batch, int num_q_heads, int num_kv_heads, int num_blocks,
+    int block_shift, int max_blocks, int num_splits, float scale, int variant,
+    int kv_fp8, hipStream_t stream) {
+  const auto kernel =
+      variant == 5 ? (kv_fp8 ? gqa_decode_attn_v5_kernel<true, true>
+                             : gqa_decode_attn_v5_kernel<false, true>)
+                   : (kv_fp8 ? gqa_decode_attn_v4_kernel<true, true>
+                             : gqa_decode_attn_v4_kernel<false, true>);
+  hipLaunchKernelGGL(kernel, dim3(batch, num_kv_heads, num_splits), dim3(256),
+                     0, stream, (bf16*)out, (float*)workspace, (const bf16*)q,
+                     k_pages, v_pages, context_lens, num_q_heads, num_kv_heads,
+                     max_blocks << block_shift, scale, block_tables,
+                     max_blocks, block_shift, num_blocks);
   if (num_splits > 1) {
     hipLaunchKernelGGL(gqa_decode_attn_merge_kernel,
                        dim3(batch, num_q_heads), dim3(64 * MERGE_WAVES), 0,

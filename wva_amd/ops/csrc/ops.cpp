@@ -33,6 +33,17 @@ extern "C" void launch_rope_append_kv(const void* qkv, void* q_out,
                                       int num_q_heads, int num_kv_heads,
                                       int head_dim, int max_seq, float theta,
                                       hipStream_t stream);
+extern "C" void launch_rope_append_kv_paged(
+    const void* qkv, void* q_out, void* k_pages, void* v_pages,
+    const int* block_tables, const int* positions, int batch, int num_q_heads,
+    int num_kv_heads, int head_dim, int num_blocks, int block_shift,
+    int max_blocks, float theta, int kv_fp8, hipStream_t stream);
+extern "C" void launch_paged_decode_attn(
+    void* out, void* workspace, const void* q, const void* k_pages,
+    const void* v_pages, const int* block_tables, const int* context_lens,
+    int batch, int num_q_heads, int num_kv_heads, int num_blocks,
+    int block_shift, int max_blocks, int num_splits, float scale, int variant,
+    int kv_fp8, hipStream_t stream);
 extern "C" int gqa_decode_attn_num_splits(int batch, int num_kv_heads,
                                           int max_ctx_hint);
 extern "C" int skinny_gemm_num_splits(int N, int K, int nt);
@@ -488,6 +499,124 @@ int64_t extend_attn_ragged_splits(int64_t batch, int64_t num_q_heads,
                                        (int)max_chunk, (int)max_seq);
 }
 
+// --- paged KV cache (csrc/attention.hip PAGED, csrc/rope.hip PAGED) ---
+
+// Shape checks shared by the two paged ops. k_pages / v_pages are
+// [num_blocks, Hk, block_size, 128]; returns log2(block_size).
+int check_paged_pool(const torch::Tensor& k_pages,
+                     const torch::Tensor& v_pages,
+                     const torch::Tensor& block_tables, int64_t batch) {
+  TORCH_CHECK(k_pages.dim() == 4 && k_pages.size(3) == 128,
+              "k_pages must be [num_blocks, Hk, block_size, 128]");
+  TORCH_CHECK(v_pages.sizes() == k_pages.sizes(), "k/v pool shape mismatch");
+  const int64_t num_blocks = k_pages.size(0);
+  const int64_t block_size = k_pages.size(2);
+  TORCH_CHECK(num_blocks >= 1, "the pool needs at least one block");
+  TORCH_CHECK(block_size == 16 || block_size == 32 || block_size == 64,
+              "block_size must be 16, 32 or 64, got ", block_size);
+  check_i32_contig(block_tables, "block_tables");
+  TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) == batch &&
+                  block_tables.size(1) >= 1,
+              "block_tables must be [B, max_blocks]");
+  // page offsets are formed in 64-bit; pool rows, table entries and
+  // positions stay in int32
+  TORCH_CHECK(num_blocks * k_pages.size(1) * block_size < (1L << 31),
+              "num_blocks * Hk * block_size must be below 2^31");
+  TORCH_CHECK(block_tables.size(1) * block_size < (1L << 31) &&
+                  batch * block_tables.size(1) < (1L << 31),
+              "block_tables too large");
+  return block_size == 16 ? 4 : block_size == 32 ? 5 : 6;
+}
+
+// Decode fast path over a paged pool: RoPE'd q_out, and the K/V row of
+// sequence b goes to page block_tables[b, pos / block_size], row pos %
+// block_size. A position past the table or an entry outside [0, num_blocks)
+// skips the K/V stores (csrc/rope.hip paged_row_offset).
+torch::Tensor rope_append_kv_paged(torch::Tensor qkv, torch::Tensor k_pages,
+                                   torch::Tensor v_pages,
+                                   torch::Tensor block_tables,
+                                   torch::Tensor positions,
+                                   int64_t num_q_heads, int64_t num_kv_heads,
+                                   double theta) {
+  check_bf16_contig(qkv, "qkv");
+  const bool fp8 = check_cache_contig(k_pages, "k_pages");
+  TORCH_CHECK(check_cache_contig(v_pages, "v_pages") == fp8,
+              "k/v pool dtype mismatch");
+  check_i32_contig(positions, "positions");
+  TORCH_CHECK(qkv.dim() == 2, "qkv must be [B, (Hq+2Hk)*D]");
+  const int batch = qkv.size(0);
+  const int block_shift =
+      check_paged_pool(k_pages, v_pages, block_tables, batch);
+  TORCH_CHECK(positions.dim() == 1 && positions.size(0) == batch,
+              "positions must be [B]");
+  const int head_dim = k_pages.size(3);
+  TORCH_CHECK(k_pages.size(1) == num_kv_heads, "Hk mismatch");
+  TORCH_CHECK(qkv.size(1) == (num_q_heads + 2 * num_kv_heads) * head_dim,
+              "qkv width mismatch");
+  auto q_out = torch::empty({batch, num_q_heads, head_dim}, qkv.options());
+  launch_rope_append_kv_paged(
+      qkv.data_ptr(), q_out.data_ptr(), k_pages.data_ptr(),
+      v_pages.data_ptr(), block_tables.data_ptr<int>(),
+      positions.data_ptr<int>(), batch, (int)num_q_heads, (int)num_kv_heads,
+      head_dim, (int)k_pages.size(0), block_shift, (int)block_tables.size(1),
+      (float)theta, fp8 ? 1 : 0, current_stream());
+  return q_out;
+}
+
+// GQA decode attention over a paged pool. The caller passes num_splits
+// (ops.paged_decode_num_splits gives the heuristic's count). `auto` applies
+// the contiguous rule, v5 when G >= 8 or unsplit, else v4; that rule was
+// measured on the contiguous layout only (profiles/attn_v4_ab.txt), see
+// docs/mi355x-kernels.md "Paged KV cache" for what pages change.
+torch::Tensor paged_decode_attn(torch::Tensor q, torch::Tensor k_pages,
+                                torch::Tensor v_pages,
+                                torch::Tensor block_tables,
+                                torch::Tensor context_lens, double scale,
+                                int64_t num_splits,
+                                const std::string& variant_name) {
+  AttnVariant variant = parse_attn_variant(variant_name);
+  check_bf16_contig(q, "q");
+  const bool kv_fp8 = check_cache_contig(k_pages, "k_pages");
+  TORCH_CHECK(check_cache_contig(v_pages, "v_pages") == kv_fp8,
+              "k/v pool dtype mismatch");
+  check_i32_contig(context_lens, "context_lens");
+  TORCH_CHECK(q.dim() == 3, "q must be [B, Hq, D]");
+  const int batch = q.size(0);
+  const int num_q_heads = q.size(1);
+  const int head_dim = q.size(2);
+  TORCH_CHECK(head_dim == 128, "head_dim must be 128 (Llama-3 family)");
+  const int block_shift =
+      check_paged_pool(k_pages, v_pages, block_tables, batch);
+  TORCH_CHECK(context_lens.dim() == 1 && context_lens.size(0) == batch,
+              "context_lens must be [B]");
+  const int num_kv_heads = k_pages.size(1);
+  TORCH_CHECK(num_q_heads % num_kv_heads == 0, "Hq must divide by Hk");
+  const int G = num_q_heads / num_kv_heads;
+  TORCH_CHECK(G <= 8, "GQA group size must be <= 8");
+  TORCH_CHECK(num_splits >= 1 && num_splits <= 65535,
+              "num_splits must be in [1, 65535]");
+  auto out = torch::empty_like(q);
+  if (variant == AttnVariant::Auto) {
+    variant = (G >= 8 || num_splits == 1) ? AttnVariant::V5 : AttnVariant::V4;
+  }
+  torch::Tensor workspace;
+  void* ws_ptr = nullptr;
+  if (num_splits > 1) {
+    workspace = torch::empty(
+        {(long)batch * num_kv_heads * G * num_splits * (2 + head_dim)},
+        q.options().dtype(torch::kFloat32));
+    ws_ptr = workspace.data_ptr();
+  }
+  launch_paged_decode_attn(
+      out.data_ptr(), ws_ptr, q.data_ptr(), k_pages.data_ptr(),
+      v_pages.data_ptr(), block_tables.data_ptr<int>(),
+      context_lens.data_ptr<int>(), batch, num_q_heads, num_kv_heads,
+      (int)k_pages.size(0), block_shift, (int)block_tables.size(1),
+      (int)num_splits, (float)scale, variant == AttnVariant::V5 ? 5 : 4,
+      kv_fp8 ? 1 : 0, current_stream());
+  return out;
+}
+
 // The m-tile grid dimension is launched at its static bound; keep it (and
 // every int index the kernels form) comfortably in range.
 void check_moe_sizes(long T, long E, long K) {
@@ -633,6 +762,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Split-KV factor gqa_decode_attn uses for a [batch, num_kv_heads, "
         "max_seq, 128] cache",
         py::arg("batch"), py::arg("num_kv_heads"), py::arg("max_seq"));
+  m.def("rope_append_kv_paged", &rope_append_kv_paged,
+        "RoPE on strided qkv row + append into a paged KV pool through "
+        "block tables; returns contiguous q",
+        py::arg("qkv"), py::arg("k_pages"), py::arg("v_pages"),
+        py::arg("block_tables"), py::arg("positions"), py::arg("num_q_heads"),
+        py::arg("num_kv_heads"), py::arg("theta") = 500000.0);
+  m.def("paged_decode_attn", &paged_decode_attn,
+        "GQA decode attention over a paged KV pool [num_blocks, Hk, "
+        "block_size, 128] through block tables [B, max_blocks]",
+        py::arg("q"), py::arg("k_pages"), py::arg("v_pages"),
+        py::arg("block_tables"), py::arg("context_lens"), py::arg("scale"),
+        py::arg("num_splits"), py::arg("variant") = "auto");
   m.def("prefill_attn", &prefill_attn,
         "Causal flash-attention prefill over head-major KV caches",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),

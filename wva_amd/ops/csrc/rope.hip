@@ -10,7 +10,9 @@
 //    and APPENDS rotated k and raw v into the KV cache at each sequence's
 //    current position — replacing 2 slice-copies + rope + 2 cache
 //    index-writes per layer with one launch
-//    (profiles/: ~13% of decode step time was this glue).
+//    (profiles/: ~13% of decode step time was this glue). The PAGED
+//    instantiations append into a paged pool [num_blocks, Hk, block_size,
+//    D] through block tables; the rotation code is the same.
 //
 // Grid: one workgroup per token; 256 threads cover heads × D/2 pairs.
 
@@ -82,6 +84,26 @@ __device__ __forceinline__ void rotate_pair_cs(
   dst[d + half] = f2bf(x2 * cs.c + x1 * cs.s);
 }
 
+// Paged append target (PAGED instantiations): sequence b's row at position
+// `pos` lives in page block_tables[b, pos / block_size], row pos %
+// block_size, of a pool [num_blocks, Hk, block_size, D]. Returns the element
+// offset of kv-head 0's row, or -1 when the row has no page: pos < 0,
+// pos / block_size >= max_blocks (the table is not read then) or a table
+// entry outside [0, num_blocks). The caller then skips the K/V stores, so a
+// corrupt table or a position past the reservation never stores out of the
+// pool; q_out is still produced.
+__device__ __forceinline__ long paged_row_offset(
+    const int* __restrict__ block_tables, int b, int pos, int max_blocks,
+    int block_shift, int num_blocks, int num_kv_heads, int head_dim) {
+  const int entry = pos >> block_shift;
+  if (pos < 0 || entry >= max_blocks) return -1;
+  const int id = block_tables[(long)b * max_blocks + entry];
+  if (id < 0 || id >= num_blocks) return -1;
+  const long row = (((long)id * num_kv_heads) << block_shift) +
+                   (pos & ((1 << block_shift) - 1));
+  return row * head_dim;
+}
+
 __global__ void rope_kernel(
     bf16* __restrict__ q,        // [T, Hq * D]
     bf16* __restrict__ k,        // [T, Hk * D]
@@ -107,22 +129,36 @@ __global__ void rope_kernel(
   }
 }
 
+template <bool PAGED>
 __global__ void rope_append_kv_kernel(
     const bf16* __restrict__ qkv,   // [B, (Hq + 2·Hk) · D]
     bf16* __restrict__ q_out,       // [B, Hq, D]
-    bf16* __restrict__ k_cache,     // [B, Hk, S_max, D] (head-major)
-    bf16* __restrict__ v_cache,     // [B, Hk, S_max, D]
+    bf16* __restrict__ k_cache,     // [B, Hk, S_max, D] (head-major);
+    bf16* __restrict__ v_cache,     // PAGED: [num_blocks, Hk, block_size, D]
     const int* __restrict__ positions,  // [B] append position per sequence
     const int num_q_heads,
     const int num_kv_heads,
     const int head_dim,
-    const int max_seq,
-    const float theta) {
+    const int max_seq,              // contiguous only
+    const float theta,
+    // PAGED only (null / 0 otherwise)
+    const int* __restrict__ block_tables,  // [B, max_blocks]
+    const int max_blocks,
+    const int block_shift,          // log2(block_size)
+    const int num_blocks) {
   const int b = blockIdx.x;
   const int pos_i = positions[b];
   const float pos = (float)pos_i;
   const int half = head_dim / 2;
   const long qkv_row = (long)b * (num_q_heads + 2 * num_kv_heads) * head_dim;
+  // element offset of kv-head 0's row and the stride between kv-heads
+  const long row0 =
+      PAGED ? paged_row_offset(block_tables, b, pos_i, max_blocks, block_shift,
+                               num_blocks, num_kv_heads, head_dim)
+            : ((long)b * num_kv_heads * max_seq + pos_i) * head_dim;
+  const long head_stride =
+      PAGED ? (long)head_dim << block_shift : (long)max_seq * head_dim;
+  const bool has_row = !PAGED || row0 >= 0;
 
   // q heads + k heads: rotate; v heads: straight copy (by 2-elem pairs)
   const int rot_total = (num_q_heads + num_kv_heads) * half;
@@ -136,9 +172,8 @@ __global__ void rope_append_kv_kernel(
     } else {
       const int kh = head - num_q_heads;
       const bf16* src = qkv + qkv_row + ((long)num_q_heads + kh) * head_dim;
-      bf16* dst = k_cache +
-          (((long)b * num_kv_heads + kh) * max_seq + pos_i) * head_dim;
-      rotate_pair(src, dst, d, half, head_dim, pos, theta);
+      bf16* dst = k_cache + row0 + kh * head_stride;
+      if (has_row) rotate_pair(src, dst, d, half, head_dim, pos, theta);
     }
   }
   // v copy: vectorized bf16x2
@@ -148,30 +183,42 @@ __global__ void rope_append_kv_kernel(
   for (int idx = threadIdx.x; idx < v_total; idx += blockDim.x) {
     const int kh = idx / half;
     const int d2 = idx % half;
-    bf16x2* dst = reinterpret_cast<bf16x2*>(
-        v_cache + (((long)b * num_kv_heads + kh) * max_seq + pos_i) * head_dim);
-    dst[d2] = vsrc[(long)kh * half + d2];
+    bf16x2* dst =
+        reinterpret_cast<bf16x2*>(v_cache + row0 + kh * head_stride);
+    if (has_row) dst[d2] = vsrc[(long)kh * half + d2];
   }
 }
 
 // fp8 (e4m3) cache variant of the decode append: q stays bf16; rotated
 // k and copied v are down-converted to 1-byte e4m3 on store (half the
 // cache bytes, double the KV capacity; see common.h fp8 helpers).
+template <bool PAGED>
 __global__ void rope_append_kv_fp8_kernel(
     const bf16* __restrict__ qkv,   // [B, (Hq + 2·Hk) · D]
     bf16* __restrict__ q_out,       // [B, Hq, D]
-    fp8_t* __restrict__ k_cache,    // [B, Hk, S_max, D] e4m3
-    fp8_t* __restrict__ v_cache,    // [B, Hk, S_max, D]
+    fp8_t* __restrict__ k_cache,    // [B, Hk, S_max, D] e4m3;
+    fp8_t* __restrict__ v_cache,    // PAGED: [num_blocks, Hk, block_size, D]
     const int* __restrict__ positions,
     const int num_q_heads,
     const int num_kv_heads,
     const int head_dim,
     const int max_seq,
-    const double log2_theta) {
+    const double log2_theta,
+    const int* __restrict__ block_tables,  // PAGED only, as in the bf16 kernel
+    const int max_blocks,
+    const int block_shift,
+    const int num_blocks) {
   const int b = blockIdx.x;
   const int pos_i = positions[b];
   const int half = head_dim / 2;
   const long qkv_row = (long)b * (num_q_heads + 2 * num_kv_heads) * head_dim;
+  const long row0 =
+      PAGED ? paged_row_offset(block_tables, b, pos_i, max_blocks, block_shift,
+                               num_blocks, num_kv_heads, head_dim)
+            : ((long)b * num_kv_heads * max_seq + pos_i) * head_dim;
+  const long head_stride =
+      PAGED ? (long)head_dim << block_shift : (long)max_seq * head_dim;
+  const bool has_row = !PAGED || row0 >= 0;
 
   const int rot_total = (num_q_heads + num_kv_heads) * half;
   RopeCosSinCache cache;
@@ -188,10 +235,11 @@ __global__ void rope_append_kv_fp8_kernel(
       const bf16* src = qkv + qkv_row + ((long)num_q_heads + kh) * head_dim;
       const float x1 = bf2f(src[d]);
       const float x2 = bf2f(src[d + half]);
-      fp8_t* dst = k_cache +
-          (((long)b * num_kv_heads + kh) * max_seq + pos_i) * head_dim;
-      dst[d] = f2fp8(x1 * cs.c - x2 * cs.s);
-      dst[d + half] = f2fp8(x2 * cs.c + x1 * cs.s);
+      fp8_t* dst = k_cache + row0 + kh * head_stride;
+      if (has_row) {
+        dst[d] = f2fp8(x1 * cs.c - x2 * cs.s);
+        dst[d + half] = f2fp8(x2 * cs.c + x1 * cs.s);
+      }
     }
   }
   // v copy: bf16x2 -> packed 2×e4m3 (adjacent dims), u16 stores
@@ -202,9 +250,9 @@ __global__ void rope_append_kv_fp8_kernel(
     const int kh = idx / half;
     const int d2 = idx % half;
     const bf16x2 v2 = vsrc[(long)kh * half + d2];
-    unsigned short* dst = reinterpret_cast<unsigned short*>(
-        v_cache + (((long)b * num_kv_heads + kh) * max_seq + pos_i) * head_dim);
-    dst[d2] = pk2_fp8(bf2f(v2.x), bf2f(v2.y));
+    unsigned short* dst =
+        reinterpret_cast<unsigned short*>(v_cache + row0 + kh * head_stride);
+    if (has_row) dst[d2] = pk2_fp8(bf2f(v2.x), bf2f(v2.y));
   }
 }
 
@@ -214,10 +262,11 @@ extern "C" void launch_rope_append_kv_fp8(
     int head_dim, int max_seq, float theta, hipStream_t stream) {
   dim3 grid(batch);
   dim3 block(256);
-  hipLaunchKernelGGL(rope_append_kv_fp8_kernel, grid, block, 0, stream,
+  hipLaunchKernelGGL(rope_append_kv_fp8_kernel<false>, grid, block, 0, stream,
                      (const bf16*)qkv, (bf16*)q_out, (fp8_t*)k_cache,
                      (fp8_t*)v_cache, positions, num_q_heads, num_kv_heads,
-                     head_dim, max_seq, log2((double)theta));
+                     head_dim, max_seq, log2((double)theta),
+                     (const int*)nullptr, 0, 0, 0);
 }
 
 extern "C" void launch_rope(
@@ -235,8 +284,32 @@ extern "C" void launch_rope_append_kv(
     int head_dim, int max_seq, float theta, hipStream_t stream) {
   dim3 grid(batch);
   dim3 block(256);
-  hipLaunchKernelGGL(rope_append_kv_kernel, grid, block, 0, stream,
+  hipLaunchKernelGGL(rope_append_kv_kernel<false>, grid, block, 0, stream,
                      (const bf16*)qkv, (bf16*)q_out, (bf16*)k_cache,
                      (bf16*)v_cache, positions, num_q_heads, num_kv_heads,
-                     head_dim, max_seq, theta);
+                     head_dim, max_seq, theta, (const int*)nullptr, 0, 0, 0);
+}
+
+// Paged append: k_pages / v_pages [num_blocks, Hk, 1 << block_shift,
+// head_dim] bf16 or e4m3 (kv_fp8), block_tables [batch, max_blocks].
+extern "C" void launch_rope_append_kv_paged(
+    const void* qkv, void* q_out, void* k_pages, void* v_pages,
+    const int* block_tables, const int* positions, int batch, int num_q_heads,
+    int num_kv_heads, int head_dim, int num_blocks, int block_shift,
+    int max_blocks, float theta, int kv_fp8, hipStream_t stream) {
+  dim3 grid(batch);
+  dim3 block(256);
+  if (kv_fp8) {
+    hipLaunchKernelGGL(rope_append_kv_fp8_kernel<true>, grid, block, 0, stream,
+                       (const bf16*)qkv, (bf16*)q_out, (fp8_t*)k_pages,
+                       (fp8_t*)v_pages, positions, num_q_heads, num_kv_heads,
+                       head_dim, 0, log2((double)theta), block_tables,
+                       max_blocks, block_shift, num_blocks);
+  } else {
+    hipLaunchKernelGGL(rope_append_kv_kernel<true>, grid, block, 0, stream,
+                       (const bf16*)qkv, (bf16*)q_out, (bf16*)k_pages,
+                       (bf16*)v_pages, positions, num_q_heads, num_kv_heads,
+                       head_dim, 0, theta, block_tables, max_blocks,
+                       block_shift, num_blocks);
+  }
 }
