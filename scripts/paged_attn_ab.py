@@ -48,9 +48,8 @@ ITL = {"batch": 64, "context_len": 512, "max_seq": 1024, "iters": 20}
 def attn_worker(spec, out_file):
     sys.path.insert(0, REPO)
     import torch
-    from wva_amd.ops import _require_ext
+    from wva_amd import ops
 
-    ext = _require_ext()
     batch, hq, hk, ctx = spec["shape"]
     fp8 = spec["fp8"]
     scale = 128 ** -0.5
@@ -64,7 +63,7 @@ def attn_worker(spec, out_file):
         return (t * 0.7).to(torch.float8_e4m3fn) if fp8 else t
 
     k, v = cache(), cache()
-    splits = int(ext.gqa_decode_attn_splits(batch, hk, ctx))
+    splits = ops.gqa_decode_num_splits(batch, hk, ctx)
 
     def pool_of(t, bs, perm):
         """Page i of the row-major (b, block) list goes to pool[perm[i]]."""
@@ -79,7 +78,7 @@ def attn_worker(spec, out_file):
     arms = {}
     for variant in VARIANTS:
         arms[f"contiguous_{variant}"] = (
-            lambda variant=variant: ext.gqa_decode_attn(
+            lambda variant=variant: ops.gqa_decode_attn(
                 q, k, v, lens, scale, variant=variant))
     for bs in BLOCK_SIZES:
         n = batch * (ctx // bs)
@@ -89,7 +88,7 @@ def attn_worker(spec, out_file):
         for variant in VARIANTS:
             arms[f"paged{bs}_{variant}"] = (
                 lambda variant=variant, kp=kp, vp=vp, tables=tables:
-                ext.paged_decode_attn(q, kp, vp, tables, lens, scale, splits,
+                ops.paged_decode_attn(q, kp, vp, tables, lens, scale, splits,
                                       variant=variant))
     for name, fn in arms.items():  # same rows, same splits: same bits
         ref = arms["contiguous_" + name.split("_")[1]]

@@ -80,13 +80,11 @@ def attn_bench():
         k = torch.randn(batch, hk, S, 128, device="cuda", dtype=torch.bfloat16)
         v = torch.randn(batch, hk, S, 128, device="cuda", dtype=torch.bfloat16)
         lens = torch.full((batch,), ctx, device="cuda", dtype=torch.int32)
-        from wva_amd.ops import _require_ext
-        ext = _require_ext()
         scale = 128 ** -0.5
         import time as _t
         for name in ("auto", "v4", "v5"):
             def fn(variant=name):
-                return ext.gqa_decode_attn(q, k, v, lens, scale,
+                return ops.gqa_decode_attn(q, k, v, lens, scale,
                                            variant=variant)
 
             for _ in range(50):
@@ -320,8 +318,7 @@ def skinny_gemm_bench():
 
     import torch
 
-    from wva_amd.ops import _require_ext
-    ext = _require_ext()
+    from wva_amd import ops
 
     shapes = [  # (label, M, N, K)
         ("qkv", 64, 6144, 4096), ("o", 64, 4096, 4096),
@@ -335,7 +332,7 @@ def skinny_gemm_bench():
         w = torch.randn(N, K, device="cuda", dtype=torch.bfloat16)
         wt = w.t()
         for name, fn in [("blaslt", lambda: x @ wt),
-                         ("skinny", lambda: ext.skinny_linear(x, w))]:
+                         ("skinny", lambda: ops.skinny_linear(x, w))]:
             for _ in range(5):
                 fn()
             torch.cuda.synchronize()

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import attn_oracle as ao
+import paged_cases as pc
 from attn_oracle import BF16, FP8
 from wva_amd import ops
 
@@ -41,7 +42,6 @@ def decode(c, variant, dev, replicas=1, splits=None, k=None, v=None):
     times (how a small case gets a grid large enough to stay unsplit).
     Asserts the split count and that every replica is bit-equal to the
     first; returns the first replica's output on the CPU."""
-    ext = ops._require_ext()
     k = c.k if k is None else k
     v = c.v if v is None else v
     B, Hk, S = k.shape[0], k.shape[1], k.shape[2]
@@ -55,7 +55,7 @@ def decode(c, variant, dev, replicas=1, splits=None, k=None, v=None):
         raw = raw.to(dev).repeat(replicas, *([1] * (t.dim() - 1)))
         return raw.view(t.dtype)
 
-    out = ext.gqa_decode_attn(rep(c.q), rep(k), rep(v), rep(c.lens), c.scale,
+    out = ops.gqa_decode_attn(rep(c.q), rep(k), rep(v), rep(c.lens), c.scale,
                               variant=variant)
     out = out.reshape(replicas, B, *out.shape[1:])
     assert torch.equal(out, out[:1].expand_as(out)), "replicas differ"
@@ -187,19 +187,56 @@ class TestDecodeRamp:
 def test_auto_dispatch_is_the_named_variant(dev, dtype):
     """`auto` is v5 when G >= 8 or the grid is unsplit, else v4: bit-equal
     to the named kernel on split and unsplit sentinel cases."""
-    ext = ops._require_ext()
     for c, splits, picked in [
         (ao.grid_case(640, dtype, 6.0), 5, "v4"),           # G = 4, split
         (ao.grid_case(64, dtype, 6.0), 1, "v5"),            # G = 4, unsplit
         (ao.edge_case(8, dtype, 6.0), ao.EDGE_SPLITS, "v5"),  # G = 8, split
     ]:
         forced = decode(c, picked, dev, splits=splits)
-        auto = ext.gqa_decode_attn(c.q.to(dev), c.k.to(dev), c.v.to(dev),
+        auto = ops.gqa_decode_attn(c.q.to(dev), c.k.to(dev), c.v.to(dev),
                                    c.lens.to(dev), c.scale).cpu()
         assert torch.equal(auto, forced), (splits, picked)
         other = decode(c, "v4" if picked == "v5" else "v5", dev,
                        splits=splits)
         assert not torch.equal(auto, other), "variants indistinguishable"
+
+
+FORCED_LENS = (130, 65)  # two tiles + two rows; one tile + one row
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("n", (1, 2, 3))
+def test_forced_splits_on_the_contiguous_op(dev, n, variant, dtype):
+    """ops.gqa_decode_attn with num_splits and variant forced, B=2, Hq=8,
+    Hk=2 over caches of 192 rows. With n = 3 the 65-row sequence has a split
+    that meets no tile (the m = -inf merge path). Finite, within the oracle
+    bound, bit-equal to ops.paged_decode_attn over the same rows at the same
+    n and variant; num_splits=None is the call forced to
+    gqa_decode_num_splits."""
+    c, ref, absref = ao.cached_ref(ao.sentinel_case, 2, 8, 2, 192,
+                                   FORCED_LENS, dtype, 31, 6.0)
+    p = pc.scatter_case(c, 16)
+
+    def put(t):  # e4m3 tensors are moved as bytes
+        return (t.view(torch.uint8).to(dev).view(FP8) if t.dtype == FP8
+                else t.to(dev))
+
+    q, k, v, lens = put(c.q), put(c.k), put(c.v), c.lens.to(dev)
+    out = ops.gqa_decode_attn(q, k, v, lens, c.scale, num_splits=n,
+                              variant=variant)
+    assert bool(torch.isfinite(out.float()).all())
+    r = check(out.cpu(), ref, absref, variant, f"forced splits n={n}")
+    paged = ops.paged_decode_attn(q, put(p.k_pages), put(p.v_pages),
+                                  p.tables.to(dev), lens, c.scale,
+                                  num_splits=n, variant=variant)
+    assert torch.equal(out, paged)
+    auto_n = ops.gqa_decode_num_splits(2, 2, 192)
+    assert torch.equal(
+        ops.gqa_decode_attn(q, k, v, lens, c.scale, variant=variant),
+        ops.gqa_decode_attn(q, k, v, lens, c.scale, num_splits=auto_n,
+                            variant=variant))
+    record("forced-splits", variant, dtype, r, f"n={n}")
 
 
 # --------------------------------------------------------------------------

@@ -70,6 +70,22 @@ class TestReferenceOps:
         out = ops.rmsnorm(x, w)
         assert out.dtype == torch.bfloat16
 
+    def test_skinny_linear_cpu_is_the_float32_matmul(self):
+        """bf16 and weight-only fp8 (w_scale): the float32 matmul, rounded
+        once to x's dtype."""
+        torch.manual_seed(4)
+        x = torch.randn(5, 256, dtype=torch.bfloat16)
+        w = (torch.randn(48, 256) * 0.05).to(torch.bfloat16)
+        y = ops.skinny_linear(x, w)
+        assert y.dtype == torch.bfloat16 and y.shape == (5, 48)
+        assert torch.equal(y, (x.float() @ w.float().t()).to(torch.bfloat16))
+
+        scale = (w.float().abs().amax(dim=1) / 448.0).clamp_min(1e-12)
+        w8 = (w.float() / scale[:, None]).to(torch.float8_e4m3fn)
+        y8 = ops.skinny_linear(x, w8, scale)
+        ref8 = x.float() @ (w8.float() * scale[:, None]).t()
+        assert torch.equal(y8, ref8.to(torch.bfloat16))
+
     def test_fit_itl_curve(self):
         from wva_amd.calibration.itl_benchmark import fit_itl_curve
 

@@ -283,9 +283,9 @@ class TestAttnV4:
                            # past 16: ~39 splits at min-tiles 8)
     ])
     def test_v4_matches_reference(self, dev, batch, hq, hk, ctx):
-        from wva_amd.ops import _require_ext, gqa_decode_attn_ref
+        from wva_amd import ops
+        from wva_amd.ops import gqa_decode_attn_ref
 
-        ext = _require_ext()
         torch.manual_seed(11)
         S = max(ctx + 8, 64)
         q = torch.randn(batch, hq, 128, device=dev, dtype=torch.bfloat16)
@@ -295,7 +295,7 @@ class TestAttnV4:
                              dtype=torch.int32)
         lens[0] = ctx
         scale = 128 ** -0.5
-        out = ext.gqa_decode_attn(q, k, v, lens, scale, variant="v4")
+        out = ops.gqa_decode_attn(q, k, v, lens, scale, variant="v4")
         ref = gqa_decode_attn_ref(
             q.float().cpu(), k.float().cpu(), v.float().cpu(),
             lens.cpu(), scale,
@@ -307,9 +307,8 @@ class TestAttnV4:
         """Pins the dispatch rule (v5 when G >= 8 or unsplit, else v4):
         `auto` must be exactly the kernel the rule names, so the outputs
         are bit-equal on the same inputs."""
-        from wva_amd.ops import _require_ext
+        from wva_amd import ops
 
-        ext = _require_ext()
         torch.manual_seed(5)
         # (8, 32, 8, 640): G = 4, 5 splits -> v4;  (2, 64, 8, 300): G = 8 -> v5
         for (batch, hq, hk, ctx), picked in [((8, 32, 8, 640), "v4"),
@@ -320,8 +319,8 @@ class TestAttnV4:
             v = torch.randn(batch, hk, ctx, 128, device=dev,
                             dtype=torch.bfloat16)
             lens = torch.full((batch,), ctx, device=dev, dtype=torch.int32)
-            a = ext.gqa_decode_attn(q, k, v, lens, 128 ** -0.5)
-            b = ext.gqa_decode_attn(q, k, v, lens, 128 ** -0.5,
+            a = ops.gqa_decode_attn(q, k, v, lens, 128 ** -0.5)
+            b = ops.gqa_decode_attn(q, k, v, lens, 128 ** -0.5,
                                     variant=picked)
             assert torch.equal(a, b), (batch, hq, hk, ctx, picked)
 
@@ -343,13 +342,12 @@ class TestSkinnyLinear:
         (64, 28672, 4096), (5, 100, 512), (64, 14336, 512),
     ])
     def test_matches_matmul(self, dev, M, N, K):
-        from wva_amd.ops import _require_ext
+        from wva_amd import ops
 
-        ext = _require_ext()
         torch.manual_seed(M * 1000 + N)
         x = torch.randn(M, K, device=dev, dtype=torch.bfloat16)
         w = torch.randn(N, K, device=dev, dtype=torch.bfloat16) * 0.05
-        y = ext.skinny_linear(x, w)
+        y = ops.skinny_linear(x, w)
         ref = (x.float() @ w.float().t())
         torch.testing.assert_close(y.float(), ref, atol=0.5, rtol=2e-2)
 
@@ -374,9 +372,9 @@ class TestAttnV5:
         (2, 8, 1, 2000),  # split path
     ])
     def test_v5_matches_reference(self, dev, batch, hq, hk, ctx):
-        from wva_amd.ops import _require_ext, gqa_decode_attn_ref
+        from wva_amd import ops
+        from wva_amd.ops import gqa_decode_attn_ref
 
-        ext = _require_ext()
         torch.manual_seed(17)
         S = max(ctx + 8, 64)
         q = torch.randn(batch, hq, 128, device=dev, dtype=torch.bfloat16)
@@ -386,7 +384,7 @@ class TestAttnV5:
                              dtype=torch.int32)
         lens[0] = ctx
         scale = 128 ** -0.5
-        out = ext.gqa_decode_attn(q, k, v, lens, scale, variant="v5")
+        out = ops.gqa_decode_attn(q, k, v, lens, scale, variant="v5")
         ref = gqa_decode_attn_ref(
             q.float().cpu(), k.float().cpu(), v.float().cpu(),
             lens.cpu(), scale,
@@ -514,9 +512,9 @@ class TestFp8KvGpu:
         """v4/v5 fp8-KV kernels vs the fp32 reference computed from the
         UPCAST cache contents (isolates kernel error from quantization
         error)."""
-        from wva_amd.ops import _require_ext, gqa_decode_attn_ref
+        from wva_amd import ops
+        from wva_amd.ops import gqa_decode_attn_ref
 
-        ext = _require_ext()
         torch.manual_seed(3)
         for B, hq, hk, ctx in [(4, 32, 8, 512), (2, 64, 8, 300),
                                (2, 8, 1, 2000)]:
@@ -533,7 +531,7 @@ class TestFp8KvGpu:
                 lens.cpu(), scale,
             )
             for variant in ("auto", "v4", "v5"):
-                out = ext.gqa_decode_attn(q, k8, v8, lens, scale,
+                out = ops.gqa_decode_attn(q, k8, v8, lens, scale,
                                           variant=variant)
                 torch.testing.assert_close(
                     out.float().cpu(), ref, atol=3e-2, rtol=3e-2
@@ -587,9 +585,8 @@ class TestFp8KvGpu:
         assert torch.isfinite(logits.float()).all()
 
     def test_skinny_linear_fp8_matches_dequant(self, dev):
-        from wva_amd.ops import _require_ext
+        from wva_amd import ops
 
-        ext = _require_ext()
         torch.manual_seed(2)
         for M, N, K in [(1, 6144, 4096), (8, 4096, 4096), (16, 4096, 14336),
                         (33, 28672, 4096)]:
@@ -598,7 +595,7 @@ class TestFp8KvGpu:
             scale = (w.abs().amax(dim=1).float() / 448.0).clamp_min(1e-12)
             w8 = ((w.float() / scale[:, None]).clamp(-448, 448)
                   .to(torch.float8_e4m3fn).contiguous())
-            y = ext.skinny_linear_fp8(x, w8, scale.contiguous())
+            y = ops.skinny_linear(x, w8, scale.contiguous())
             ref = x.float() @ (w8.float() * scale[:, None]).t()
             torch.testing.assert_close(y.float(), ref, atol=0.5, rtol=2e-2)
 

@@ -5,7 +5,7 @@ LlamaDecodeModel(kv_layout="paged") eager and under a captured graph.
 Two conditions throughout:
   * oracle: within attn_oracle.attn_bound of the cached float64 reference
     of the contiguous case (p_bf16 for v5);
-  * bit-equality: torch.equal to ext.gqa_decode_attn on the contiguous case
+  * bit-equality: torch.equal to ops.gqa_decode_attn on the contiguous case
     with the same pinned variant and the split count of the contiguous
     launch. The paged kernels change addresses only, so no rounding may
     differ; the condition is derived, not tuned.
@@ -68,13 +68,13 @@ def contiguous(c, variant, dev, splits):
     assert ops.gqa_decode_num_splits(B, Hk, S) == splits, (
         "the launch heuristic no longer splits this shape as the test "
         "assumes")
-    return ops._require_ext().gqa_decode_attn(
+    return ops.gqa_decode_attn(
         put(c.q, dev), put(c.k, dev), put(c.v, dev), c.lens.to(dev), c.scale,
         variant=variant).cpu()
 
 
 def paged(c, p, variant, dev, splits):
-    return ops._require_ext().paged_decode_attn(
+    return ops.paged_decode_attn(
         put(c.q, dev), put(p.k_pages, dev), put(p.v_pages, dev),
         p.tables.to(dev), c.lens.to(dev), c.scale, splits,
         variant=variant).cpu()

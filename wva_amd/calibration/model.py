@@ -360,14 +360,9 @@ class LlamaDecodeModel:
         w8, w_scale = (
             getattr(layer, name + "_q") if layer is not None else self.lm_head_q
         )
-        if not x.is_cuda:  # CPU reference: dequantized matmul
-            return (
-                x.float() @ (w8.float() * w_scale[:, None]).t()
-            ).to(x.dtype)
-        if x.shape[0] <= 64 and x.shape[1] % 128 == 0:
-            from .. import ops as _ops
-
-            return _ops._require_ext().skinny_linear_fp8(x, w8, w_scale)
+        # CPU: the dequantized matmul reference, at any size
+        if not x.is_cuda or (x.shape[0] <= 64 and x.shape[1] % 128 == 0):
+            return ops.skinny_linear(x, w8, w_scale)
         # large-M fallback (prefill-scale): dequantize and use hipBLASLt
         return (x @ (w8.to(x.dtype) * w_scale[:, None].to(x.dtype)).t())
 

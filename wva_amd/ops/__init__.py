@@ -472,12 +472,18 @@ def gqa_decode_attn(
     v_cache: torch.Tensor,
     context_lens: torch.Tensor,
     scale: Optional[float] = None,
+    num_splits: Optional[int] = None,
+    variant: str = "auto",
 ) -> torch.Tensor:
+    """GQA decode attention over contiguous head-major caches [B, Hk, S,
+    128]. `num_splits` and `variant` are those of paged_decode_attn; None
+    asks gqa_decode_num_splits over S."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     if q.is_cuda:
         return _require_ext().gqa_decode_attn(
-            q, k_cache, v_cache, context_lens.to(torch.int32), scale
+            q, k_cache, v_cache, context_lens.to(torch.int32), scale,
+            variant, num_splits,
         )
     return gqa_decode_attn_ref(q, k_cache, v_cache, context_lens, scale).to(
         q.dtype
@@ -527,11 +533,6 @@ def paged_decode_attn(
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     if q.is_cuda:
-        if num_splits is None:
-            num_splits = paged_decode_num_splits(
-                q.shape[0], k_pages.shape[1], block_tables.shape[1],
-                k_pages.shape[2],
-            )
         return _require_ext().paged_decode_attn(
             q, k_pages, v_pages, block_tables.to(torch.int32),
             context_lens.to(torch.int32), scale, num_splits, variant,
@@ -631,27 +632,38 @@ def enable_tuned_gemms() -> bool:
     mismatched stack TunableOp discards them and falls back to defaults.
     Returns True if the table was loaded.
     """
-    import os as _os
-
-    import torch as _torch
-
-    path = _os.path.join(_os.path.dirname(__file__), "tunableop_gfx950.csv")
-    if not _torch.cuda.is_available() or not _os.path.exists(path):
+    path = os.path.join(_HERE, "tunableop_gfx950.csv")
+    if not torch.cuda.is_available() or not os.path.exists(path):
         return False
-    tun = _torch.cuda.tunable
+    tun = torch.cuda.tunable
     tun.enable(True)
     tun.tuning_enable(False)  # read-only: never autotune in production
     tun.read_file(path)
     return True
 
 
+def skinny_linear(
+    x: torch.Tensor, w: torch.Tensor, w_scale: Optional[torch.Tensor] = None
+) -> torch.Tensor:
+    """y = x @ w.T ([M,K] @ [N,K]^T, M <= 64, K % 128 == 0) on the
+    weight-streaming MFMA kernel (csrc/skinny_gemm.hip). With `w_scale` [N]
+    the weights are weight-only fp8: w is float8_e4m3fn with per-channel
+    float32 scales and y = x @ (w * w_scale[:, None]).T. On CPU it is that
+    matmul in float32."""
+    if x.is_cuda:
+        if w_scale is None:
+            return _require_ext().skinny_linear(x, w)
+        return _require_ext().skinny_linear_fp8(x, w, w_scale)
+    wf = w.float() if w_scale is None else w.float() * w_scale[:, None]
+    return (x.float() @ wf.t()).to(x.dtype)
+
+
 def linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """Decode linear y = x @ w.T ([M,K] @ [N,K]^T).
 
     Dispatch is measurement-driven and currently ALWAYS hipBLASLt: the
-    in-tree weight-streaming MFMA kernel (csrc/skinny_gemm.hip, exposed
-    as ext.skinny_linear) beat hipBLASLt on isolated small-N/small-M
-    microbenches but loses IN CONTEXT inside the decode step, where the
+    in-tree weight-streaming MFMA kernel (skinny_linear) beat hipBLASLt on
+    isolated small-N/small-M microbenches but loses IN CONTEXT inside the decode step, where the
     activation matrix is not L2-hot between layers (decode b=1 measured
     5.27 ms/step pure-blaslt vs 5.41 with the kernel dispatched on
     qkv/o). Full history: profiles/skinny_gemm_ab.txt and
@@ -666,7 +678,7 @@ def linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
         and x.shape[1] <= 8192
         and w.shape[0] <= 8192
     ):
-        return _require_ext().skinny_linear(x, w)
+        return skinny_linear(x, w)
     return x @ w.t()
 
 

@@ -27,7 +27,10 @@
 // suffice (the k-sum is permutation-invariant), C/D is col = lane&15,
 // row = (lane>>4)·4 + reg.
 //
+// Host side: one entry, launch_gqa_decode_attn (declared in launch.h), picks
+// the instantiation for both layouts and launches the merge.
 #include "common.h"
+#include "launch.h"
 
 #include <type_traits>
 
@@ -867,52 +870,30 @@ extern "C" int gqa_decode_attn_num_splits(int batch, int num_kv_heads,
   return splits < 1 ? 1 : splits;
 }
 
-// Launch the chosen kernel (variant 4 or 5, bf16 or fp8 cache) on a
-// (batch, num_kv_heads, num_splits) grid, then the merge when the context
-// was split. `workspace` holds batch·num_q_heads·num_splits·(2+128)
-// floats; it may be null when num_splits == 1.
+// The v4/v5 × bf16/fp8 choice of one layout; all eight instantiations share
+// one signature.
+template <bool PAGED>
+static auto decode_attn_kernel(int variant, int kv_fp8) {
+  return variant == 5 ? (kv_fp8 ? gqa_decode_attn_v5_kernel<true, PAGED>
+                                : gqa_decode_attn_v5_kernel<false, PAGED>)
+                      : (kv_fp8 ? gqa_decode_attn_v4_kernel<true, PAGED>
+                                : gqa_decode_attn_v4_kernel<false, PAGED>);
+}
+
 extern "C" void launch_gqa_decode_attn(
     void* out, void* workspace, const void* q, const void* k_cache,
-    const void* v_cache, const int* context_lens, int batch, int num_q_heads,
-    int num_kv_heads, int max_seq, int num_splits, float scale, int variant,
-    int kv_fp8, hipStream_t stream) {
-  const auto kernel =
-      variant == 5 ? (kv_fp8 ? gqa_decode_attn_v5_kernel<true, false>
-                             : gqa_decode_attn_v5_kernel<false, false>)
-                   : (kv_fp8 ? gqa_decode_attn_v4_kernel<true, false>
-                             : gqa_decode_attn_v4_kernel<false, false>);
+    const void* v_cache, const int* context_lens, const PagedKV* paged,
+    int batch, int num_q_heads, int num_kv_heads, int max_seq, int num_splits,
+    float scale, int variant, int kv_fp8, hipStream_t stream) {
+  const auto kernel = !paged ? decode_attn_kernel<false>(variant, kv_fp8)
+                             : decode_attn_kernel<true>(variant, kv_fp8);
+  const PagedKV p = paged ? *paged : PagedKV{nullptr, 0, 0, 0};
+  if (paged) max_seq = p.max_blocks << p.block_shift;
   hipLaunchKernelGGL(kernel, dim3(batch, num_kv_heads, num_splits), dim3(256),
                      0, stream, (bf16*)out, (float*)workspace, (const bf16*)q,
                      k_cache, v_cache, context_lens, num_q_heads, num_kv_heads,
-                     max_seq, scale, (const int*)nullptr, 0, 0, 0);
-  if (num_splits > 1) {
-    hipLaunchKernelGGL(gqa_decode_attn_merge_kernel,
-                       dim3(batch, num_q_heads), dim3(64 * MERGE_WAVES), 0,
-                       stream, (bf16*)out, (const float*)workspace,
-                       num_q_heads, num_kv_heads, num_splits);
-  }
-}
-
-// The same over a paged pool: k_pages / v_pages [num_blocks, Hk, block_size,
-// 128] with block_size = 1 << block_shift in {16, 32, 64}, block_tables
-// [batch, max_blocks]. Same grid, workspace and merge as the contiguous
-// launch; the caller picks num_splits.
-extern "C" void launch_paged_decode_attn(
-    void* out, void* workspace, const void* q, const void* k_pages,
-    const void* v_pages, const int* block_tables, const int* context_lens,
-    int batch, int num_q_heads, int num_kv_heads, int num_blocks,
-    int block_shift, int max_blocks, int num_splits, float scale, int variant,
-    int kv_fp8, hipStream_t stream) {
-  const auto kernel =
-      variant == 5 ? (kv_fp8 ? gqa_decode_attn_v5_kernel<true, true>
-                             : gqa_decode_attn_v5_kernel<false, true>)
-                   : (kv_fp8 ? gqa_decode_attn_v4_kernel<true, true>
-                             : gqa_decode_attn_v4_kernel<false, true>);
-  hipLaunchKernelGGL(kernel, dim3(batch, num_kv_heads, num_splits), dim3(256),
-                     0, stream, (bf16*)out, (float*)workspace, (const bf16*)q,
-                     k_pages, v_pages, context_lens, num_q_heads, num_kv_heads,
-                     max_blocks << block_shift, scale, block_tables,
-                     max_blocks, block_shift, num_blocks);
+                     max_seq, scale, p.block_tables, p.max_blocks,
+                     p.block_shift, p.num_blocks);
   if (num_splits > 1) {
     hipLaunchKernelGGL(gqa_decode_attn_merge_kernel,
                        dim3(batch, num_q_heads), dim3(64 * MERGE_WAVES), 0,

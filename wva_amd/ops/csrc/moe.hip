@@ -27,6 +27,7 @@
 // C/D mapping col = lane&15 (n), row = (lane>>4)·4 + reg (m).
 
 #include "common.h"
+#include "launch.h"
 
 #define MOE_KT 128      // K elements per unrolled block
 #define MOE_BM 64       // sorted rows per m-tile (4 MFMA m-subtiles)

@@ -1,109 +1,18 @@
 // Torch bindings for the wva_amd MI355X (gfx950) kernels.
 //
-// Built in-tree via torch.utils.cpp_extension (PYTORCH_ROCM_ARCH=gfx950);
-// the .so travels with the repo snapshot to GPU boxes.
+// Built in-tree via torch.utils.cpp_extension (PYTORCH_ROCM_ARCH=gfx950).
+// The kernels' host entry points are declared in launch.h, which the .hip
+// files include too; nothing is re-declared here. Each kernel family has one
+// implementation below (decode attention, KV append, skinny linear, prefill
+// operands) behind its contiguous/paged or bf16/fp8 bindings, so a check or
+// a launch argument is edited in one place.
 
 #include <torch/extension.h>
-#include <hip/hip_runtime.h>
 #include <c10/hip/HIPStream.h>
 
 #include <string>
 
-extern "C" void launch_rmsnorm(void* out, void* residual_out,
-                               const void* input, const void* residual,
-                               const void* weight, float eps, int rows,
-                               int hidden, hipStream_t stream);
-extern "C" void launch_rope(void* q, void* k, const int* positions, int tokens,
-                            int num_q_heads, int num_k_heads, int head_dim,
-                            float theta, hipStream_t stream);
-extern "C" void launch_silu_mul(void* out, const void* gate, const void* up,
-                                long n, hipStream_t stream);
-extern "C" void launch_silu_mul_fused(void* out, const void* gate_up,
-                                      long rows, long inter,
-                                      hipStream_t stream);
-extern "C" void launch_rope_append_kv_fp8(const void* qkv, void* q_out,
-                                          void* k_cache, void* v_cache,
-                                          const int* positions, int batch,
-                                          int num_q_heads, int num_kv_heads,
-                                          int head_dim, int max_seq,
-                                          float theta, hipStream_t stream);
-extern "C" void launch_rope_append_kv(const void* qkv, void* q_out,
-                                      void* k_cache, void* v_cache,
-                                      const int* positions, int batch,
-                                      int num_q_heads, int num_kv_heads,
-                                      int head_dim, int max_seq, float theta,
-                                      hipStream_t stream);
-extern "C" void launch_rope_append_kv_paged(
-    const void* qkv, void* q_out, void* k_pages, void* v_pages,
-    const int* block_tables, const int* positions, int batch, int num_q_heads,
-    int num_kv_heads, int head_dim, int num_blocks, int block_shift,
-    int max_blocks, float theta, int kv_fp8, hipStream_t stream);
-extern "C" void launch_paged_decode_attn(
-    void* out, void* workspace, const void* q, const void* k_pages,
-    const void* v_pages, const int* block_tables, const int* context_lens,
-    int batch, int num_q_heads, int num_kv_heads, int num_blocks,
-    int block_shift, int max_blocks, int num_splits, float scale, int variant,
-    int kv_fp8, hipStream_t stream);
-extern "C" int gqa_decode_attn_num_splits(int batch, int num_kv_heads,
-                                          int max_ctx_hint);
-extern "C" int skinny_gemm_num_splits(int N, int K, int nt);
-extern "C" void launch_prefill_attn_ex(void* out, const void* q,
-                                       const void* k_cache,
-                                       const void* v_cache, int batch,
-                                       int seq, int num_q_heads,
-                                       int num_kv_heads, int max_seq,
-                                       float scale, int kv_fp8,
-                                       hipStream_t stream);
-extern "C" void launch_extend_attn(void* out, const void* q,
-                                   const void* k_cache, const void* v_cache,
-                                   const int* prefix_lens, int batch,
-                                   int chunk, int num_q_heads,
-                                   int num_kv_heads, int max_seq, float scale,
-                                   int kv_fp8, hipStream_t stream);
-extern "C" int extend_attn_ragged_num_splits(int batch, int num_q_heads,
-                                             int max_chunk, int max_seq);
-extern "C" void launch_extend_attn_ragged(
-    void* out, void* ws, const void* q, const void* k_cache,
-    const void* v_cache, const int* prefix_lens, const int* q_starts,
-    const int* chunk_lens, int batch, int total_rows, int max_chunk,
-    int num_q_heads, int num_kv_heads, int max_seq, int num_splits,
-    float scale, int kv_fp8, hipStream_t stream);
-extern "C" int skinny_gemm_tile_n(int M);
-extern "C" void launch_skinny_gemm(void* c, void* ws, const void* a,
-                                   const void* w, int M, int N, int K,
-                                   int num_splits, hipStream_t stream);
-extern "C" void launch_skinny_gemm_ex(void* c, void* ws, const void* a,
-                                      const void* w, const float* w_scale,
-                                      int M, int N, int K, int num_splits,
-                                      int w_fp8, hipStream_t stream);
-extern "C" void launch_gqa_decode_attn(void* out, void* workspace,
-                                       const void* q, const void* k_cache,
-                                       const void* v_cache,
-                                       const int* context_lens, int batch,
-                                       int num_q_heads, int num_kv_heads,
-                                       int max_seq, int num_splits,
-                                       float scale, int variant, int kv_fp8,
-                                       hipStream_t stream);
-
-extern "C" int moe_num_m_tiles(int TK, int E);
-extern "C" int moe_down_num_splits(int TK, int E, int H, int I);
-extern "C" void launch_moe_route(int* topk_idx, float* topk_w,
-                                 int* expert_offsets, int* sorted_slots,
-                                 const float* logits, int T, int E, int K,
-                                 hipStream_t stream);
-extern "C" void launch_moe_gate_up_swiglu(void* act, const void* x,
-                                          const void* w,
-                                          const int* expert_offsets,
-                                          const int* sorted_slots, int T,
-                                          int E, int top_k, int H, int I,
-                                          hipStream_t stream);
-extern "C" void launch_moe_down_combine(void* out, float* ws,
-                                        const void* act, const void* w,
-                                        const float* topk_w,
-                                        const int* expert_offsets,
-                                        const int* sorted_slots, int T,
-                                        int E, int top_k, int H, int I,
-                                        int num_splits, hipStream_t stream);
+#include "launch.h"
 
 namespace {
 
@@ -117,15 +26,53 @@ void check_bf16_contig(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
-// KV caches may be bf16 or fp8 e4m3 (torch float8_e4m3fn); returns true
-// when the cache is fp8.
-bool check_cache_contig(const torch::Tensor& t, const char* name) {
+void check_i32_contig(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == torch::kInt32, name, " must be int32");
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-  if (t.scalar_type() == torch::kBFloat16) return false;
-  TORCH_CHECK(t.scalar_type() == at::kFloat8_e4m3fn,
-              name, " must be bf16 or float8_e4m3fn");
-  return true;
+}
+
+// A K/V cache (or paged pool) pair: both on the GPU and contiguous, the same
+// dtype, bf16 or fp8 e4m3 (torch float8_e4m3fn), and the same shape. Returns
+// true when the pair is fp8.
+bool check_kv_pair(const torch::Tensor& k, const torch::Tensor& v) {
+  TORCH_CHECK(k.is_cuda() && v.is_cuda(), "k/v cache must be on GPU");
+  TORCH_CHECK(k.is_contiguous() && v.is_contiguous(),
+              "k/v cache must be contiguous");
+  const bool fp8 = k.scalar_type() == at::kFloat8_e4m3fn;
+  TORCH_CHECK(fp8 || k.scalar_type() == torch::kBFloat16,
+              "k/v cache must be bf16 or float8_e4m3fn");
+  TORCH_CHECK(v.scalar_type() == k.scalar_type(), "k/v cache dtype mismatch");
+  TORCH_CHECK(v.sizes() == k.sizes(), "k/v cache shape mismatch");
+  return fp8;
+}
+
+// Paged operands shared by the decode attention and KV append ops: k_pages
+// (and v_pages, see check_kv_pair) are [num_blocks, Hk, block_size, 128],
+// block_tables [B, max_blocks]. Returns the launch descriptor.
+PagedKV check_paged_pool(const torch::Tensor& k_pages,
+                         const torch::Tensor& block_tables, int64_t batch) {
+  TORCH_CHECK(k_pages.dim() == 4 && k_pages.size(3) == 128,
+              "k_pages must be [num_blocks, Hk, block_size, 128]");
+  const int64_t num_blocks = k_pages.size(0);
+  const int64_t block_size = k_pages.size(2);
+  TORCH_CHECK(num_blocks >= 1, "the pool needs at least one block");
+  TORCH_CHECK(block_size == 16 || block_size == 32 || block_size == 64,
+              "block_size must be 16, 32 or 64, got ", block_size);
+  check_i32_contig(block_tables, "block_tables");
+  TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) == batch &&
+                  block_tables.size(1) >= 1,
+              "block_tables must be [B, max_blocks]");
+  // page offsets are formed in 64-bit; pool rows, table entries and
+  // positions stay in int32
+  TORCH_CHECK(num_blocks * k_pages.size(1) * block_size < (1L << 31),
+              "num_blocks * Hk * block_size must be below 2^31");
+  TORCH_CHECK(block_tables.size(1) * block_size < (1L << 31) &&
+                  batch * block_tables.size(1) < (1L << 31),
+              "block_tables too large");
+  return PagedKV{block_tables.data_ptr<int>(), (int)block_tables.size(1),
+                 block_size == 16 ? 4 : block_size == 32 ? 5 : 6,
+                 (int)num_blocks};
 }
 
 // out = rmsnorm(input [+ residual]) * weight; when residual is given it is
@@ -158,8 +105,7 @@ void rope(torch::Tensor q, torch::Tensor k, torch::Tensor positions,
           double theta) {
   check_bf16_contig(q, "q");
   check_bf16_contig(k, "k");
-  TORCH_CHECK(positions.is_cuda() && positions.scalar_type() == torch::kInt32,
-              "positions must be int32 on GPU");
+  check_i32_contig(positions, "positions");
   TORCH_CHECK(q.dim() == 3 && k.dim() == 3, "q/k must be [T, H, D]");
   const int tokens = q.size(0);
   const int num_q_heads = q.size(1);
@@ -183,32 +129,63 @@ torch::Tensor silu_mul(torch::Tensor gate, torch::Tensor up) {
   return out;
 }
 
-// Decode fast path: strided qkv row → RoPE'd q_out + cache append.
-torch::Tensor rope_append_kv(torch::Tensor qkv, torch::Tensor k_cache,
-                             torch::Tensor v_cache, torch::Tensor positions,
-                             int64_t num_q_heads, int64_t num_kv_heads,
-                             double theta) {
+// Decode fast path: strided qkv row → RoPE'd q_out + cache append at
+// positions[b]. Contiguous caches are [>= B, Hk, S, D]. With block_tables the
+// caches are a paged pool and the K/V row of sequence b goes to page
+// block_tables[b, pos / block_size], row pos % block_size; a position past
+// the table or an entry outside [0, num_blocks) skips the K/V stores
+// (csrc/rope.hip paged_row_offset).
+torch::Tensor rope_append_kv_impl(
+    const torch::Tensor& qkv, const torch::Tensor& k_cache,
+    const torch::Tensor& v_cache,
+    const c10::optional<torch::Tensor>& block_tables,
+    const torch::Tensor& positions, int64_t num_q_heads, int64_t num_kv_heads,
+    double theta) {
   check_bf16_contig(qkv, "qkv");
-  const bool fp8 = check_cache_contig(k_cache, "k_cache");
-  TORCH_CHECK(check_cache_contig(v_cache, "v_cache") == fp8,
-              "k/v cache dtype mismatch");
-  TORCH_CHECK(positions.is_cuda() && positions.scalar_type() == torch::kInt32,
-              "positions must be int32 on GPU");
+  const bool kv_fp8 = check_kv_pair(k_cache, v_cache);
+  check_i32_contig(positions, "positions");
   TORCH_CHECK(qkv.dim() == 2, "qkv must be [B, (Hq+2Hk)*D]");
-  TORCH_CHECK(k_cache.dim() == 4, "k_cache must be [B, Hk, S, D]");
   const int batch = qkv.size(0);
+  TORCH_CHECK(positions.dim() == 1 && positions.size(0) == batch,
+              "positions must be [B]");
+  PagedKV paged{};
+  if (block_tables.has_value()) {
+    paged = check_paged_pool(k_cache, *block_tables, batch);
+  } else {
+    TORCH_CHECK(k_cache.dim() == 4, "k_cache must be [B, Hk, S, D]");
+    TORCH_CHECK(k_cache.size(0) >= batch,
+                "cache holds fewer than B sequences");
+  }
   const int head_dim = k_cache.size(3);
-  const int max_seq = k_cache.size(2);
   TORCH_CHECK(k_cache.size(1) == num_kv_heads, "Hk mismatch");
   TORCH_CHECK(qkv.size(1) == (num_q_heads + 2 * num_kv_heads) * head_dim,
               "qkv width mismatch");
   auto q_out = torch::empty({batch, num_q_heads, head_dim}, qkv.options());
-  auto launch = fp8 ? launch_rope_append_kv_fp8 : launch_rope_append_kv;
-  launch(qkv.data_ptr(), q_out.data_ptr(), k_cache.data_ptr(),
-         v_cache.data_ptr(), positions.data_ptr<int>(), batch,
-         (int)num_q_heads, (int)num_kv_heads, head_dim, max_seq,
-         (float)theta, current_stream());
+  launch_rope_append_kv(qkv.data_ptr(), q_out.data_ptr(), k_cache.data_ptr(),
+                        v_cache.data_ptr(), positions.data_ptr<int>(),
+                        block_tables.has_value() ? &paged : nullptr, batch,
+                        (int)num_q_heads, (int)num_kv_heads, head_dim,
+                        (int)k_cache.size(2), (float)theta, kv_fp8 ? 1 : 0,
+                        current_stream());
   return q_out;
+}
+
+torch::Tensor rope_append_kv(torch::Tensor qkv, torch::Tensor k_cache,
+                             torch::Tensor v_cache, torch::Tensor positions,
+                             int64_t num_q_heads, int64_t num_kv_heads,
+                             double theta) {
+  return rope_append_kv_impl(qkv, k_cache, v_cache, c10::nullopt, positions,
+                             num_q_heads, num_kv_heads, theta);
+}
+
+torch::Tensor rope_append_kv_paged(torch::Tensor qkv, torch::Tensor k_pages,
+                                   torch::Tensor v_pages,
+                                   torch::Tensor block_tables,
+                                   torch::Tensor positions,
+                                   int64_t num_q_heads, int64_t num_kv_heads,
+                                   double theta) {
+  return rope_append_kv_impl(qkv, k_pages, v_pages, block_tables, positions,
+                             num_q_heads, num_kv_heads, theta);
 }
 
 torch::Tensor silu_mul_fused(torch::Tensor gate_up) {
@@ -240,37 +217,57 @@ AttnVariant parse_attn_variant(const std::string& name) {
                         : AttnVariant::Auto;
 }
 
-torch::Tensor gqa_decode_attn(torch::Tensor q, torch::Tensor k_cache,
-                              torch::Tensor v_cache,
-                              torch::Tensor context_lens, double scale,
-                              const std::string& variant_name) {
+// GQA decode attention, q/out [B, Hq, 128], context_lens [B]. Contiguous
+// caches are [>= B, Hk, S, 128]; with block_tables they are a paged pool
+// (check_paged_pool). num_splits absent means the launch heuristic over S,
+// or over max_blocks * block_size for a pool. On a pool `auto` applies the
+// rule above as it stands; it was measured on the contiguous layout only,
+// see docs/mi355x-kernels.md "Paged KV cache" for what pages change.
+torch::Tensor decode_attn_impl(
+    const torch::Tensor& q, const torch::Tensor& k_cache,
+    const torch::Tensor& v_cache,
+    const c10::optional<torch::Tensor>& block_tables,
+    const torch::Tensor& context_lens, double scale,
+    c10::optional<int64_t> forced_splits, const std::string& variant_name) {
   AttnVariant variant = parse_attn_variant(variant_name);
   check_bf16_contig(q, "q");
-  const bool kv_fp8 = check_cache_contig(k_cache, "k_cache");
-  TORCH_CHECK(check_cache_contig(v_cache, "v_cache") == kv_fp8,
-              "k/v cache dtype mismatch");
-  TORCH_CHECK(context_lens.is_cuda() &&
-                  context_lens.scalar_type() == torch::kInt32,
-              "context_lens must be int32 on GPU");
+  const bool kv_fp8 = check_kv_pair(k_cache, v_cache);
+  check_i32_contig(context_lens, "context_lens");
   TORCH_CHECK(q.dim() == 3, "q must be [B, Hq, D]");
-  TORCH_CHECK(k_cache.dim() == 4,
-              "k_cache must be [B, Hk, S, D] (head-major)");
   const int batch = q.size(0);
   const int num_q_heads = q.size(1);
   const int head_dim = q.size(2);
-  const int num_kv_heads = k_cache.size(1);
-  const int max_seq = k_cache.size(2);
   TORCH_CHECK(head_dim == 128, "head_dim must be 128 (Llama-3 family)");
+  TORCH_CHECK(context_lens.dim() == 1 && context_lens.size(0) == batch,
+              "context_lens must be [B]");
+  PagedKV paged{};
+  int max_seq;
+  if (block_tables.has_value()) {
+    paged = check_paged_pool(k_cache, *block_tables, batch);
+    max_seq = paged.max_blocks << paged.block_shift;
+  } else {
+    TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(3) == 128,
+                "k_cache must be [B, Hk, S, 128] (head-major)");
+    TORCH_CHECK(k_cache.size(0) >= batch,
+                "cache holds fewer than B sequences");
+    max_seq = k_cache.size(2);
+  }
+  const int num_kv_heads = k_cache.size(1);
   TORCH_CHECK(num_q_heads % num_kv_heads == 0, "Hq must divide by Hk");
   const int G = num_q_heads / num_kv_heads;
   TORCH_CHECK(G <= 8, "GQA group size must be <= 8");
-  TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), "k/v cache mismatch");
-  auto out = torch::empty_like(q);
+  if (forced_splits.has_value()) {
+    TORCH_CHECK(*forced_splits >= 1 && *forced_splits <= 65535,
+                "num_splits must be in [1, 65535]");
+  }
   const int num_splits =
-      gqa_decode_attn_num_splits(batch, num_kv_heads, max_seq);
+      forced_splits.has_value()
+          ? (int)*forced_splits
+          : gqa_decode_attn_num_splits(batch, num_kv_heads, max_seq);
   if (variant == AttnVariant::Auto) {
     variant = (G >= 8 || num_splits == 1) ? AttnVariant::V5 : AttnVariant::V4;
   }
+  auto out = torch::empty_like(q);
   torch::Tensor workspace;
   void* ws_ptr = nullptr;
   if (num_splits > 1) {
@@ -281,11 +278,31 @@ torch::Tensor gqa_decode_attn(torch::Tensor q, torch::Tensor k_cache,
   }
   launch_gqa_decode_attn(out.data_ptr(), ws_ptr, q.data_ptr(),
                          k_cache.data_ptr(), v_cache.data_ptr(),
-                         context_lens.data_ptr<int>(), batch, num_q_heads,
-                         num_kv_heads, max_seq, num_splits, (float)scale,
-                         variant == AttnVariant::V5 ? 5 : 4, kv_fp8 ? 1 : 0,
-                         current_stream());
+                         context_lens.data_ptr<int>(),
+                         block_tables.has_value() ? &paged : nullptr, batch,
+                         num_q_heads, num_kv_heads, max_seq, num_splits,
+                         (float)scale, variant == AttnVariant::V5 ? 5 : 4,
+                         kv_fp8 ? 1 : 0, current_stream());
   return out;
+}
+
+torch::Tensor gqa_decode_attn(torch::Tensor q, torch::Tensor k_cache,
+                              torch::Tensor v_cache,
+                              torch::Tensor context_lens, double scale,
+                              const std::string& variant,
+                              c10::optional<int64_t> num_splits) {
+  return decode_attn_impl(q, k_cache, v_cache, c10::nullopt, context_lens,
+                          scale, num_splits, variant);
+}
+
+torch::Tensor paged_decode_attn(torch::Tensor q, torch::Tensor k_pages,
+                                torch::Tensor v_pages,
+                                torch::Tensor block_tables,
+                                torch::Tensor context_lens, double scale,
+                                c10::optional<int64_t> num_splits,
+                                const std::string& variant) {
+  return decode_attn_impl(q, k_pages, v_pages, block_tables, context_lens,
+                          scale, num_splits, variant);
 }
 
 int64_t gqa_decode_attn_splits(int64_t batch, int64_t num_kv_heads,
@@ -296,10 +313,28 @@ int64_t gqa_decode_attn_splits(int64_t batch, int64_t num_kv_heads,
 
 // Decode linear: y[M,N] = x[M,K] @ w[N,K]^T on the weight-streaming
 // MFMA kernel (csrc/skinny_gemm.hip). Caller guarantees M <= 64 and
-// K % 128 == 0; larger M belongs to hipBLASLt.
-torch::Tensor skinny_linear(torch::Tensor x, torch::Tensor w) {
+// K % 128 == 0; larger M belongs to hipBLASLt. With w_scale the weights are
+// weight-only fp8 (W8A16): w is [N, K] e4m3 with per-channel scales [N];
+// activations stay bf16, dequantization happens in-fragment and the scale
+// folds into the store (W_FP8).
+torch::Tensor skinny_linear_impl(const torch::Tensor& x,
+                                 const torch::Tensor& w,
+                                 const c10::optional<torch::Tensor>& w_scale) {
   check_bf16_contig(x, "x");
-  check_bf16_contig(w, "w");
+  const float* scale_ptr = nullptr;
+  if (w_scale.has_value()) {
+    TORCH_CHECK(w.is_cuda() && w.is_contiguous() &&
+                    w.scalar_type() == at::kFloat8_e4m3fn,
+                "w must be contiguous float8_e4m3fn");
+    TORCH_CHECK(w_scale->is_cuda() &&
+                    w_scale->scalar_type() == torch::kFloat &&
+                    w_scale->is_contiguous() && w.dim() == 2 &&
+                    w_scale->numel() == w.size(0),
+                "w_scale must be float32 [N]");
+    scale_ptr = w_scale->data_ptr<float>();
+  } else {
+    check_bf16_contig(w, "w");
+  }
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2, "x [M,K], w [N,K]");
   const int M = x.size(0);
   const int K = x.size(1);
@@ -308,8 +343,7 @@ torch::Tensor skinny_linear(torch::Tensor x, torch::Tensor w) {
   TORCH_CHECK(M <= 64, "skinny_linear requires M <= 64");
   TORCH_CHECK(K % 128 == 0, "K must be a multiple of 128");
   auto y = torch::empty({M, N}, x.options());
-  const int nt = skinny_gemm_tile_n(M);
-  const int sk = skinny_gemm_num_splits(N, K, nt);
+  const int sk = skinny_gemm_num_splits(N, K, skinny_gemm_tile_n(M));
   torch::Tensor ws;
   void* ws_ptr = nullptr;
   if (sk > 1) {
@@ -317,44 +351,44 @@ torch::Tensor skinny_linear(torch::Tensor x, torch::Tensor w) {
                       x.options().dtype(torch::kFloat32));
     ws_ptr = ws.data_ptr();
   }
-  launch_skinny_gemm(y.data_ptr(), ws_ptr, x.data_ptr(), w.data_ptr(), M, N,
-                     K, sk, current_stream());
+  launch_skinny_gemm(y.data_ptr(), ws_ptr, x.data_ptr(), w.data_ptr(),
+                     scale_ptr, M, N, K, sk, scale_ptr ? 1 : 0,
+                     current_stream());
   return y;
 }
 
-// Weight-only fp8 (W8A16): w is [N, K] e4m3 with per-channel scales [N];
-// activations stay bf16, dequantization happens in-fragment and the
-// scale folds into the store (csrc/skinny_gemm.hip W_FP8).
+torch::Tensor skinny_linear(torch::Tensor x, torch::Tensor w) {
+  return skinny_linear_impl(x, w, c10::nullopt);
+}
+
 torch::Tensor skinny_linear_fp8(torch::Tensor x, torch::Tensor w,
                                 torch::Tensor w_scale) {
-  check_bf16_contig(x, "x");
-  TORCH_CHECK(w.is_cuda() && w.is_contiguous() &&
-                  w.scalar_type() == at::kFloat8_e4m3fn,
-              "w must be contiguous float8_e4m3fn");
-  TORCH_CHECK(w_scale.is_cuda() && w_scale.scalar_type() == torch::kFloat &&
-                  w_scale.numel() == w.size(0),
-              "w_scale must be float32 [N]");
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2, "x [M,K], w [N,K]");
-  const int M = x.size(0);
-  const int K = x.size(1);
-  const int N = w.size(0);
-  TORCH_CHECK(w.size(1) == K, "K mismatch");
-  TORCH_CHECK(M <= 64, "skinny_linear requires M <= 64");
-  TORCH_CHECK(K % 128 == 0, "K must be a multiple of 128");
-  auto y = torch::empty({M, N}, x.options());
-  const int nt = skinny_gemm_tile_n(M);
-  const int sk = skinny_gemm_num_splits(N, K, nt);
-  torch::Tensor ws;
-  void* ws_ptr = nullptr;
-  if (sk > 1) {
-    ws = torch::empty({(long)sk * M * N},
-                      x.options().dtype(torch::kFloat32));
-    ws_ptr = ws.data_ptr();
-  }
-  launch_skinny_gemm_ex(y.data_ptr(), ws_ptr, x.data_ptr(), w.data_ptr(),
-                        w_scale.data_ptr<float>(), M, N, K, sk, 1,
-                        current_stream());
-  return y;
+  return skinny_linear_impl(x, w, w_scale);
+}
+
+// Operand checks shared by prefill_attn, extend_attn and extend_attn_ragged:
+// q [T, Hq, 128] bf16 against head-major caches [>= batch, Hk, S_max, 128]
+// with G = Hq / Hk <= 8.
+struct PrefillOperands {
+  bool kv_fp8;
+  int num_q_heads, num_kv_heads, max_seq;
+};
+
+PrefillOperands check_prefill_operands(const torch::Tensor& q,
+                                       const torch::Tensor& k_cache,
+                                       const torch::Tensor& v_cache,
+                                       int64_t batch) {
+  check_bf16_contig(q, "q");
+  const bool kv_fp8 = check_kv_pair(k_cache, v_cache);
+  TORCH_CHECK(q.dim() == 3 && q.size(2) == 128, "q must be [T, Hq, 128]");
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(3) == 128,
+              "k_cache must be [B, Hk, S_max, 128]");
+  TORCH_CHECK(k_cache.size(0) >= batch, "cache holds fewer than B sequences");
+  const int num_q_heads = q.size(1);
+  const int num_kv_heads = k_cache.size(1);
+  TORCH_CHECK(num_q_heads % num_kv_heads == 0, "Hq must divide by Hk");
+  TORCH_CHECK(num_q_heads / num_kv_heads <= 8, "GQA group size must be <= 8");
+  return {kv_fp8, num_q_heads, num_kv_heads, (int)k_cache.size(2)};
 }
 
 // Causal flash-attention prefill over the (already-populated) head-major
@@ -362,33 +396,16 @@ torch::Tensor skinny_linear_fp8(torch::Tensor x, torch::Tensor w,
 torch::Tensor prefill_attn(torch::Tensor q, torch::Tensor k_cache,
                            torch::Tensor v_cache, int64_t batch, int64_t seq,
                            double scale) {
-  check_bf16_contig(q, "q");
-  const bool kv_fp8 = check_cache_contig(k_cache, "k_cache");
-  TORCH_CHECK(check_cache_contig(v_cache, "v_cache") == kv_fp8,
-              "k/v cache dtype mismatch");
-  TORCH_CHECK(q.dim() == 3 && q.size(2) == 128, "q must be [T, Hq, 128]");
-  TORCH_CHECK(q.size(0) == batch * seq, "T must equal B*S");
-  TORCH_CHECK(k_cache.dim() == 4, "k_cache must be [B, Hk, S_max, D]");
-  const int num_q_heads = q.size(1);
-  const int num_kv_heads = k_cache.size(1);
-  const int max_seq = k_cache.size(2);
-  TORCH_CHECK(seq <= max_seq, "seq exceeds cache size");
-  TORCH_CHECK(num_q_heads % num_kv_heads == 0, "Hq must divide by Hk");
-  TORCH_CHECK(num_q_heads / num_kv_heads <= 8, "GQA group size must be <= 8");
+  const PrefillOperands p = check_prefill_operands(q, k_cache, v_cache, batch);
+  TORCH_CHECK(batch >= 0 && seq >= 0 && q.size(0) == batch * seq,
+              "T must equal B*S");
+  TORCH_CHECK(seq <= p.max_seq, "seq exceeds cache size");
   auto out = torch::empty_like(q);
-  launch_prefill_attn_ex(out.data_ptr(), q.data_ptr(), k_cache.data_ptr(),
-                         v_cache.data_ptr(), (int)batch, (int)seq,
-                         num_q_heads, num_kv_heads, max_seq, (float)scale,
-                         kv_fp8 ? 1 : 0, current_stream());
+  launch_prefill_attn(out.data_ptr(), q.data_ptr(), k_cache.data_ptr(),
+                      v_cache.data_ptr(), nullptr, (int)batch, (int)seq,
+                      p.num_q_heads, p.num_kv_heads, p.max_seq, (float)scale,
+                      p.kv_fp8 ? 1 : 0, current_stream());
   return out;
-}
-
-// --- routed MoE expert MLP (csrc/moe.hip) ---
-
-void check_i32_contig(const torch::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-  TORCH_CHECK(t.scalar_type() == torch::kInt32, name, " must be int32");
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
 // Chunked prefill ("extend") attention: `chunk` new query rows per sequence
@@ -399,32 +416,20 @@ void check_i32_contig(const torch::Tensor& t, const char* name) {
 torch::Tensor extend_attn(torch::Tensor q, torch::Tensor k_cache,
                           torch::Tensor v_cache, torch::Tensor prefix_lens,
                           int64_t chunk, double scale) {
-  check_bf16_contig(q, "q");
-  const bool kv_fp8 = check_cache_contig(k_cache, "k_cache");
-  TORCH_CHECK(check_cache_contig(v_cache, "v_cache") == kv_fp8,
-              "k/v cache dtype mismatch");
   check_i32_contig(prefix_lens, "prefix_lens");
-  TORCH_CHECK(q.dim() == 3 && q.size(2) == 128, "q must be [T, Hq, 128]");
-  TORCH_CHECK(chunk >= 1 && q.size(0) % chunk == 0,
-              "T must be a multiple of chunk");
+  TORCH_CHECK(q.dim() == 3 && chunk >= 1 && q.size(0) % chunk == 0,
+              "q must be [T, Hq, 128] with T a multiple of chunk");
   const int64_t batch = q.size(0) / chunk;
+  const PrefillOperands p = check_prefill_operands(q, k_cache, v_cache, batch);
   TORCH_CHECK(prefix_lens.dim() == 1 && prefix_lens.size(0) == batch,
               "prefix_lens must be [B] with B = T / chunk");
-  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(3) == 128,
-              "k_cache must be [B, Hk, S_max, 128]");
-  TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), "k/v cache shape mismatch");
-  TORCH_CHECK(k_cache.size(0) >= batch, "cache holds fewer than B sequences");
-  const int num_q_heads = q.size(1);
-  const int num_kv_heads = k_cache.size(1);
-  const int max_seq = k_cache.size(2);
-  TORCH_CHECK(chunk <= max_seq, "chunk exceeds cache size");
-  TORCH_CHECK(num_q_heads % num_kv_heads == 0, "Hq must divide by Hk");
-  TORCH_CHECK(num_q_heads / num_kv_heads <= 8, "GQA group size must be <= 8");
+  TORCH_CHECK(chunk <= p.max_seq, "chunk exceeds cache size");
   auto out = torch::empty_like(q);
-  launch_extend_attn(out.data_ptr(), q.data_ptr(), k_cache.data_ptr(),
-                     v_cache.data_ptr(), prefix_lens.data_ptr<int>(),
-                     (int)batch, (int)chunk, num_q_heads, num_kv_heads,
-                     max_seq, (float)scale, kv_fp8 ? 1 : 0, current_stream());
+  launch_prefill_attn(out.data_ptr(), q.data_ptr(), k_cache.data_ptr(),
+                      v_cache.data_ptr(), prefix_lens.data_ptr<int>(),
+                      (int)batch, (int)chunk, p.num_q_heads, p.num_kv_heads,
+                      p.max_seq, (float)scale, p.kv_fp8 ? 1 : 0,
+                      current_stream());
   return out;
 }
 
@@ -440,33 +445,21 @@ torch::Tensor extend_attn_ragged(torch::Tensor q, torch::Tensor k_cache,
                                  torch::Tensor q_starts,
                                  torch::Tensor chunk_lens, int64_t max_chunk,
                                  double scale, int64_t num_splits) {
-  check_bf16_contig(q, "q");
-  const bool kv_fp8 = check_cache_contig(k_cache, "k_cache");
-  TORCH_CHECK(check_cache_contig(v_cache, "v_cache") == kv_fp8,
-              "k/v cache dtype mismatch");
   check_i32_contig(prefix_lens, "prefix_lens");
   check_i32_contig(q_starts, "q_starts");
   check_i32_contig(chunk_lens, "chunk_lens");
-  TORCH_CHECK(q.dim() == 3 && q.size(2) == 128, "q must be [T, Hq, 128]");
-  TORCH_CHECK(q.size(0) >= 1, "need at least one query row");
   TORCH_CHECK(chunk_lens.dim() == 1 && chunk_lens.size(0) >= 1,
               "chunk_lens must be [B] with B >= 1");
   const int64_t batch = chunk_lens.size(0);
+  const PrefillOperands p = check_prefill_operands(q, k_cache, v_cache, batch);
+  const int num_q_heads = p.num_q_heads;
+  TORCH_CHECK(q.size(0) >= 1, "need at least one query row");
   TORCH_CHECK(prefix_lens.dim() == 1 && prefix_lens.size(0) == batch,
               "prefix_lens must be [B] like chunk_lens");
   TORCH_CHECK(q_starts.dim() == 1 && q_starts.size(0) == batch,
               "q_starts must be [B] like chunk_lens");
-  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(3) == 128,
-              "k_cache must be [B, Hk, S_max, 128]");
-  TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), "k/v cache shape mismatch");
-  TORCH_CHECK(k_cache.size(0) >= batch, "cache holds fewer than B sequences");
-  const int num_q_heads = q.size(1);
-  const int num_kv_heads = k_cache.size(1);
-  const int max_seq = k_cache.size(2);
-  TORCH_CHECK(max_chunk >= 1 && max_chunk <= max_seq,
+  TORCH_CHECK(max_chunk >= 1 && max_chunk <= p.max_seq,
               "max_chunk must be in [1, cache size]");
-  TORCH_CHECK(num_q_heads % num_kv_heads == 0, "Hq must divide by Hk");
-  TORCH_CHECK(num_q_heads / num_kv_heads <= 8, "GQA group size must be <= 8");
   TORCH_CHECK(q.size(0) < (1L << 31) / num_q_heads, "T * Hq too large");
   const int64_t tiles = (max_chunk + 63) / 64;
   TORCH_CHECK(tiles <= 65535 && batch * num_q_heads < (1L << 31),
@@ -488,8 +481,8 @@ torch::Tensor extend_attn_ragged(torch::Tensor q, torch::Tensor k_cache,
       out.data_ptr(), ws_ptr, q.data_ptr(), k_cache.data_ptr(),
       v_cache.data_ptr(), prefix_lens.data_ptr<int>(),
       q_starts.data_ptr<int>(), chunk_lens.data_ptr<int>(), (int)batch,
-      (int)q.size(0), (int)max_chunk, num_q_heads, num_kv_heads, max_seq,
-      (int)num_splits, (float)scale, kv_fp8 ? 1 : 0, current_stream());
+      (int)q.size(0), (int)max_chunk, num_q_heads, p.num_kv_heads, p.max_seq,
+      (int)num_splits, (float)scale, p.kv_fp8 ? 1 : 0, current_stream());
   return out;
 }
 
@@ -499,123 +492,7 @@ int64_t extend_attn_ragged_splits(int64_t batch, int64_t num_q_heads,
                                        (int)max_chunk, (int)max_seq);
 }
 
-// --- paged KV cache (csrc/attention.hip PAGED, csrc/rope.hip PAGED) ---
-
-// Shape checks shared by the two paged ops. k_pages / v_pages are
-// [num_blocks, Hk, block_size, 128]; returns log2(block_size).
-int check_paged_pool(const torch::Tensor& k_pages,
-                     const torch::Tensor& v_pages,
-                     const torch::Tensor& block_tables, int64_t batch) {
-  TORCH_CHECK(k_pages.dim() == 4 && k_pages.size(3) == 128,
-              "k_pages must be [num_blocks, Hk, block_size, 128]");
-  TORCH_CHECK(v_pages.sizes() == k_pages.sizes(), "k/v pool shape mismatch");
-  const int64_t num_blocks = k_pages.size(0);
-  const int64_t block_size = k_pages.size(2);
-  TORCH_CHECK(num_blocks >= 1, "the pool needs at least one block");
-  TORCH_CHECK(block_size == 16 || block_size == 32 || block_size == 64,
-              "block_size must be 16, 32 or 64, got ", block_size);
-  check_i32_contig(block_tables, "block_tables");
-  TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) == batch &&
-                  block_tables.size(1) >= 1,
-              "block_tables must be [B, max_blocks]");
-  // page offsets are formed in 64-bit; pool rows, table entries and
-  // positions stay in int32
-  TORCH_CHECK(num_blocks * k_pages.size(1) * block_size < (1L << 31),
-              "num_blocks * Hk * block_size must be below 2^31");
-  TORCH_CHECK(block_tables.size(1) * block_size < (1L << 31) &&
-                  batch * block_tables.size(1) < (1L << 31),
-              "block_tables too large");
-  return block_size == 16 ? 4 : block_size == 32 ? 5 : 6;
-}
-
-// Decode fast path over a paged pool: RoPE'd q_out, and the K/V row of
-// sequence b goes to page block_tables[b, pos / block_size], row pos %
-// block_size. A position past the table or an entry outside [0, num_blocks)
-// skips the K/V stores (csrc/rope.hip paged_row_offset).
-torch::Tensor rope_append_kv_paged(torch::Tensor qkv, torch::Tensor k_pages,
-                                   torch::Tensor v_pages,
-                                   torch::Tensor block_tables,
-                                   torch::Tensor positions,
-                                   int64_t num_q_heads, int64_t num_kv_heads,
-                                   double theta) {
-  check_bf16_contig(qkv, "qkv");
-  const bool fp8 = check_cache_contig(k_pages, "k_pages");
-  TORCH_CHECK(check_cache_contig(v_pages, "v_pages") == fp8,
-              "k/v pool dtype mismatch");
-  check_i32_contig(positions, "positions");
-  TORCH_CHECK(qkv.dim() == 2, "qkv must be [B, (Hq+2Hk)*D]");
-  const int batch = qkv.size(0);
-  const int block_shift =
-      check_paged_pool(k_pages, v_pages, block_tables, batch);
-  TORCH_CHECK(positions.dim() == 1 && positions.size(0) == batch,
-              "positions must be [B]");
-  const int head_dim = k_pages.size(3);
-  TORCH_CHECK(k_pages.size(1) == num_kv_heads, "Hk mismatch");
-  TORCH_CHECK(qkv.size(1) == (num_q_heads + 2 * num_kv_heads) * head_dim,
-              "qkv width mismatch");
-  auto q_out = torch::empty({batch, num_q_heads, head_dim}, qkv.options());
-  launch_rope_append_kv_paged(
-      qkv.data_ptr(), q_out.data_ptr(), k_pages.data_ptr(),
-      v_pages.data_ptr(), block_tables.data_ptr<int>(),
-      positions.data_ptr<int>(), batch, (int)num_q_heads, (int)num_kv_heads,
-      head_dim, (int)k_pages.size(0), block_shift, (int)block_tables.size(1),
-      (float)theta, fp8 ? 1 : 0, current_stream());
-  return q_out;
-}
-
-// GQA decode attention over a paged pool. The caller passes num_splits
-// (ops.paged_decode_num_splits gives the heuristic's count). `auto` applies
-// the contiguous rule, v5 when G >= 8 or unsplit, else v4; that rule was
-// measured on the contiguous layout only (profiles/attn_v4_ab.txt), see
-// docs/mi355x-kernels.md "Paged KV cache" for what pages change.
-torch::Tensor paged_decode_attn(torch::Tensor q, torch::Tensor k_pages,
-                                torch::Tensor v_pages,
-                                torch::Tensor block_tables,
-                                torch::Tensor context_lens, double scale,
-                                int64_t num_splits,
-                                const std::string& variant_name) {
-  AttnVariant variant = parse_attn_variant(variant_name);
-  check_bf16_contig(q, "q");
-  const bool kv_fp8 = check_cache_contig(k_pages, "k_pages");
-  TORCH_CHECK(check_cache_contig(v_pages, "v_pages") == kv_fp8,
-              "k/v pool dtype mismatch");
-  check_i32_contig(context_lens, "context_lens");
-  TORCH_CHECK(q.dim() == 3, "q must be [B, Hq, D]");
-  const int batch = q.size(0);
-  const int num_q_heads = q.size(1);
-  const int head_dim = q.size(2);
-  TORCH_CHECK(head_dim == 128, "head_dim must be 128 (Llama-3 family)");
-  const int block_shift =
-      check_paged_pool(k_pages, v_pages, block_tables, batch);
-  TORCH_CHECK(context_lens.dim() == 1 && context_lens.size(0) == batch,
-              "context_lens must be [B]");
-  const int num_kv_heads = k_pages.size(1);
-  TORCH_CHECK(num_q_heads % num_kv_heads == 0, "Hq must divide by Hk");
-  const int G = num_q_heads / num_kv_heads;
-  TORCH_CHECK(G <= 8, "GQA group size must be <= 8");
-  TORCH_CHECK(num_splits >= 1 && num_splits <= 65535,
-              "num_splits must be in [1, 65535]");
-  auto out = torch::empty_like(q);
-  if (variant == AttnVariant::Auto) {
-    variant = (G >= 8 || num_splits == 1) ? AttnVariant::V5 : AttnVariant::V4;
-  }
-  torch::Tensor workspace;
-  void* ws_ptr = nullptr;
-  if (num_splits > 1) {
-    workspace = torch::empty(
-        {(long)batch * num_kv_heads * G * num_splits * (2 + head_dim)},
-        q.options().dtype(torch::kFloat32));
-    ws_ptr = workspace.data_ptr();
-  }
-  launch_paged_decode_attn(
-      out.data_ptr(), ws_ptr, q.data_ptr(), k_pages.data_ptr(),
-      v_pages.data_ptr(), block_tables.data_ptr<int>(),
-      context_lens.data_ptr<int>(), batch, num_q_heads, num_kv_heads,
-      (int)k_pages.size(0), block_shift, (int)block_tables.size(1),
-      (int)num_splits, (float)scale, variant == AttnVariant::V5 ? 5 : 4,
-      kv_fp8 ? 1 : 0, current_stream());
-  return out;
-}
+// --- routed MoE expert MLP (csrc/moe.hip) ---
 
 // The m-tile grid dimension is launched at its static bound; keep it (and
 // every int index the kernels form) comfortably in range.
@@ -754,10 +631,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("theta") = 500000.0);
   m.def("gqa_decode_attn", &gqa_decode_attn,
         "GQA decode attention over contiguous KV cache; variant pins the "
-        "kernel (\"v4\", \"v5\") instead of the measured dispatch (\"auto\")",
+        "kernel (\"v4\", \"v5\") instead of the measured dispatch (\"auto\"), "
+        "num_splits the split-KV factor instead of the launch heuristic",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("context_lens"), py::arg("scale"),
-        py::arg("variant") = "auto");
+        py::arg("variant") = "auto", py::arg("num_splits") = py::none());
   m.def("gqa_decode_attn_splits", &gqa_decode_attn_splits,
         "Split-KV factor gqa_decode_attn uses for a [batch, num_kv_heads, "
         "max_seq, 128] cache",
@@ -773,7 +651,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "block_size, 128] through block tables [B, max_blocks]",
         py::arg("q"), py::arg("k_pages"), py::arg("v_pages"),
         py::arg("block_tables"), py::arg("context_lens"), py::arg("scale"),
-        py::arg("num_splits"), py::arg("variant") = "auto");
+        py::arg("num_splits") = py::none(), py::arg("variant") = "auto");
   m.def("prefill_attn", &prefill_attn,
         "Causal flash-attention prefill over head-major KV caches",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),

@@ -29,6 +29,7 @@
 // C/D mapping is col = lane&15, row = (lane>>4)·4 + reg.
 
 #include "common.h"
+#include "launch.h"
 
 #define HEAD_DIM 128
 #define QT 64              // query rows per workgroup
@@ -467,19 +468,6 @@ __global__ __launch_bounds__(64 * MERGE_ROWS) void extend_ragged_merge_kernel(
   orow[lane] = bf16x2{f2bf(o0 * inv), f2bf(o1 * inv)};
 }
 
-extern "C" void launch_prefill_attn_ex(
-    void* out, const void* q, const void* k_cache, const void* v_cache,
-    int batch, int seq, int num_q_heads, int num_kv_heads, int max_seq,
-    float scale, int kv_fp8, hipStream_t stream);
-
-extern "C" void launch_prefill_attn(
-    void* out, const void* q, const void* k_cache, const void* v_cache,
-    int batch, int seq, int num_q_heads, int num_kv_heads, int max_seq,
-    float scale, hipStream_t stream) {
-  launch_prefill_attn_ex(out, q, k_cache, v_cache, batch, seq, num_q_heads,
-                         num_kv_heads, max_seq, scale, 0, stream);
-}
-
 template <bool HAS_PREFIX>
 static void launch_prefill_kernel(
     void* out, const void* q, const void* k_cache, const void* v_cache,
@@ -503,25 +491,20 @@ static void launch_prefill_kernel(
   }
 }
 
-extern "C" void launch_prefill_attn_ex(
+extern "C" void launch_prefill_attn(
     void* out, const void* q, const void* k_cache, const void* v_cache,
-    int batch, int seq, int num_q_heads, int num_kv_heads, int max_seq,
-    float scale, int kv_fp8, hipStream_t stream) {
-  launch_prefill_kernel<false>(out, q, k_cache, v_cache, nullptr, batch, seq,
-                               num_q_heads, num_kv_heads, max_seq, scale,
-                               kv_fp8, stream);
-}
-
-// Chunked prefill: `chunk` query rows per sequence at the device-side
-// offsets prefix_lens[b]; grid = (B·Hq, ceil(chunk/64)).
-extern "C" void launch_extend_attn(
-    void* out, const void* q, const void* k_cache, const void* v_cache,
-    const int* prefix_lens, int batch, int chunk, int num_q_heads,
+    const int* prefix_lens, int batch, int rows, int num_q_heads,
     int num_kv_heads, int max_seq, float scale, int kv_fp8,
     hipStream_t stream) {
-  launch_prefill_kernel<true>(out, q, k_cache, v_cache, prefix_lens, batch,
-                              chunk, num_q_heads, num_kv_heads, max_seq,
-                              scale, kv_fp8, stream);
+  if (!prefix_lens) {
+    launch_prefill_kernel<false>(out, q, k_cache, v_cache, nullptr, batch,
+                                 rows, num_q_heads, num_kv_heads, max_seq,
+                                 scale, kv_fp8, stream);
+  } else {
+    launch_prefill_kernel<true>(out, q, k_cache, v_cache, prefix_lens, batch,
+                                rows, num_q_heads, num_kv_heads, max_seq,
+                                scale, kv_fp8, stream);
+  }
 }
 
 // Split count of the ragged extend launch from static shapes only (the
@@ -548,11 +531,6 @@ extern "C" int extend_attn_ragged_num_splits(int batch, int num_q_heads,
   return splits < 1 ? 1 : splits;
 }
 
-// Ragged chunked prefill: sequence b owns chunk_lens[b] <= max_chunk packed
-// rows of q/out from q_starts[b]; grid = (B·Hq, ceil(max_chunk/64),
-// num_splits), then the merge when the sweep was split. `ws` holds
-// B·Hq·ceil(max_chunk/64)·64·num_splits·(2+128) floats and may be null when
-// num_splits == 1. Nothing is read back: graph-capturable.
 extern "C" void launch_extend_attn_ragged(
     void* out, void* ws, const void* q, const void* k_cache,
     const void* v_cache, const int* prefix_lens, const int* q_starts,

@@ -8,6 +8,7 @@
 // vector path requires H % 8 == 0 (checked host-side).
 
 #include "common.h"
+#include "launch.h"
 
 typedef __attribute__((ext_vector_type(4))) float floatx4;
 

@@ -17,6 +17,7 @@
 // Grid: one workgroup per token; 256 threads cover heads × D/2 pairs.
 
 #include "common.h"
+#include "launch.h"
 
 // bf16 destinations: float32 inv_freq and angle, hardware sin/cos (which
 // reduces its argument itself). Measured against a float64 rotation this
@@ -256,19 +257,6 @@ __global__ void rope_append_kv_fp8_kernel(
   }
 }
 
-extern "C" void launch_rope_append_kv_fp8(
-    const void* qkv, void* q_out, void* k_cache, void* v_cache,
-    const int* positions, int batch, int num_q_heads, int num_kv_heads,
-    int head_dim, int max_seq, float theta, hipStream_t stream) {
-  dim3 grid(batch);
-  dim3 block(256);
-  hipLaunchKernelGGL(rope_append_kv_fp8_kernel<false>, grid, block, 0, stream,
-                     (const bf16*)qkv, (bf16*)q_out, (fp8_t*)k_cache,
-                     (fp8_t*)v_cache, positions, num_q_heads, num_kv_heads,
-                     head_dim, max_seq, log2((double)theta),
-                     (const int*)nullptr, 0, 0, 0);
-}
-
 extern "C" void launch_rope(
     void* q, void* k, const int* positions, int tokens, int num_q_heads,
     int num_k_heads, int head_dim, float theta, hipStream_t stream) {
@@ -278,38 +266,45 @@ extern "C" void launch_rope(
                      positions, num_q_heads, num_k_heads, head_dim, theta);
 }
 
-extern "C" void launch_rope_append_kv(
+// The bf16 / e4m3 instantiation of one layout; the fp8 kernel takes
+// log2(theta) as a double.
+template <bool PAGED>
+static void launch_append_kernel(
     const void* qkv, void* q_out, void* k_cache, void* v_cache,
-    const int* positions, int batch, int num_q_heads, int num_kv_heads,
-    int head_dim, int max_seq, float theta, hipStream_t stream) {
-  dim3 grid(batch);
-  dim3 block(256);
-  hipLaunchKernelGGL(rope_append_kv_kernel<false>, grid, block, 0, stream,
-                     (const bf16*)qkv, (bf16*)q_out, (bf16*)k_cache,
-                     (bf16*)v_cache, positions, num_q_heads, num_kv_heads,
-                     head_dim, max_seq, theta, (const int*)nullptr, 0, 0, 0);
-}
-
-// Paged append: k_pages / v_pages [num_blocks, Hk, 1 << block_shift,
-// head_dim] bf16 or e4m3 (kv_fp8), block_tables [batch, max_blocks].
-extern "C" void launch_rope_append_kv_paged(
-    const void* qkv, void* q_out, void* k_pages, void* v_pages,
-    const int* block_tables, const int* positions, int batch, int num_q_heads,
-    int num_kv_heads, int head_dim, int num_blocks, int block_shift,
-    int max_blocks, float theta, int kv_fp8, hipStream_t stream) {
+    const int* positions, const PagedKV& p, int batch, int num_q_heads,
+    int num_kv_heads, int head_dim, int max_seq, float theta, int kv_fp8,
+    hipStream_t stream) {
   dim3 grid(batch);
   dim3 block(256);
   if (kv_fp8) {
-    hipLaunchKernelGGL(rope_append_kv_fp8_kernel<true>, grid, block, 0, stream,
-                       (const bf16*)qkv, (bf16*)q_out, (fp8_t*)k_pages,
-                       (fp8_t*)v_pages, positions, num_q_heads, num_kv_heads,
-                       head_dim, 0, log2((double)theta), block_tables,
-                       max_blocks, block_shift, num_blocks);
+    hipLaunchKernelGGL(rope_append_kv_fp8_kernel<PAGED>, grid, block, 0,
+                       stream, (const bf16*)qkv, (bf16*)q_out, (fp8_t*)k_cache,
+                       (fp8_t*)v_cache, positions, num_q_heads, num_kv_heads,
+                       head_dim, max_seq, log2((double)theta), p.block_tables,
+                       p.max_blocks, p.block_shift, p.num_blocks);
   } else {
-    hipLaunchKernelGGL(rope_append_kv_kernel<true>, grid, block, 0, stream,
-                       (const bf16*)qkv, (bf16*)q_out, (bf16*)k_pages,
-                       (bf16*)v_pages, positions, num_q_heads, num_kv_heads,
-                       head_dim, 0, theta, block_tables, max_blocks,
-                       block_shift, num_blocks);
+    hipLaunchKernelGGL(rope_append_kv_kernel<PAGED>, grid, block, 0, stream,
+                       (const bf16*)qkv, (bf16*)q_out, (bf16*)k_cache,
+                       (bf16*)v_cache, positions, num_q_heads, num_kv_heads,
+                       head_dim, max_seq, theta, p.block_tables, p.max_blocks,
+                       p.block_shift, p.num_blocks);
+  }
+}
+
+// The paged kernels take no max_seq (0), the contiguous ones no table.
+extern "C" void launch_rope_append_kv(
+    const void* qkv, void* q_out, void* k_cache, void* v_cache,
+    const int* positions, const PagedKV* paged, int batch, int num_q_heads,
+    int num_kv_heads, int head_dim, int max_seq, float theta, int kv_fp8,
+    hipStream_t stream) {
+  if (!paged) {
+    launch_append_kernel<false>(qkv, q_out, k_cache, v_cache, positions,
+                                PagedKV{nullptr, 0, 0, 0}, batch, num_q_heads,
+                                num_kv_heads, head_dim, max_seq, theta, kv_fp8,
+                                stream);
+  } else {
+    launch_append_kernel<true>(qkv, q_out, k_cache, v_cache, positions,
+                               *paged, batch, num_q_heads, num_kv_heads,
+                               head_dim, 0, theta, kv_fp8, stream);
   }
 }

@@ -4,6 +4,7 @@
 // vectorized; flat 1-D grid sized ≫ 256 workgroups so all 8 XCDs fill.
 
 #include "common.h"
+#include "launch.h"
 
 __global__ void silu_mul_kernel(
     bf16* __restrict__ out,

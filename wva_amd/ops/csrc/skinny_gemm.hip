@@ -27,6 +27,7 @@
 // col = lane&15 (n), row = (lane>>4)·4 + reg (m).
 
 #include "common.h"
+#include "launch.h"
 
 #define KT 128          // K elements per unrolled block
 #define NT 64           // W rows per workgroup (16 per wave)
@@ -185,10 +186,10 @@ extern "C" int skinny_gemm_num_splits(int N, int K, int nt) {
   return sk;
 }
 
-extern "C" void launch_skinny_gemm_ex(void* c, void* ws, const void* a,
-                                      const void* w, const float* w_scale,
-                                      int M, int N, int K, int num_splits,
-                                      int w_fp8, hipStream_t stream) {
+extern "C" void launch_skinny_gemm(void* c, void* ws, const void* a,
+                                   const void* w, const float* w_scale, int M,
+                                   int N, int K, int num_splits, int w_fp8,
+                                   hipStream_t stream) {
   const int nt = (M > 16) ? 2 * NT : NT;
   dim3 grid((N + nt - 1) / nt, num_splits);
   dim3 block(256);
@@ -221,13 +222,6 @@ extern "C" void launch_skinny_gemm_ex(void* c, void* ws, const void* a,
     hipLaunchKernelGGL(skinny_gemm_merge_kernel, mgrid, block, 0, stream,
                        (bf16*)c, (const float*)ws, num_splits, MN);
   }
-}
-
-extern "C" void launch_skinny_gemm(void* c, void* ws, const void* a,
-                                   const void* w, int M, int N, int K,
-                                   int num_splits, hipStream_t stream) {
-  launch_skinny_gemm_ex(c, ws, a, w, nullptr, M, N, K, num_splits, 0,
-                        stream);
 }
 
 extern "C" int skinny_gemm_tile_n(int M) { return (M > 16) ? 2 * NT : NT; }
