@@ -658,6 +658,13 @@ def skinny_linear(
     return (x.float() @ wf.t()).to(x.dtype)
 
 
+def skinny_linear_num_splits(M: int, N: int, K: int) -> int:
+    """Split-K factor skinny_linear picks for x [M, K] and w [N, K]
+    (1 = unsplit, no workspace and no merge). Static shapes only; the same
+    for bf16 and fp8 weights."""
+    return int(_require_ext().skinny_linear_splits(M, N, K))
+
+
 def linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """Decode linear y = x @ w.T ([M,K] @ [N,K]^T).
 

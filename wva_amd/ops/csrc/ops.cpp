@@ -84,7 +84,6 @@ torch::Tensor rmsnorm(torch::Tensor input, torch::Tensor weight,
   const int hidden = input.size(-1);
   TORCH_CHECK(hidden % 8 == 0, "hidden must be a multiple of 8");
   TORCH_CHECK(weight.numel() == hidden, "weight size mismatch");
-  const long rows = input.numel() / hidden;
   auto out = torch::empty_like(input);
   const void* res_ptr = nullptr;
   void* res_out_ptr = nullptr;
@@ -94,6 +93,9 @@ torch::Tensor rmsnorm(torch::Tensor input, torch::Tensor weight,
     res_ptr = residual->data_ptr();
     res_out_ptr = residual->data_ptr();  // in-place fold
   }
+  // no rows (or hidden == 0): a zero-sized grid is an invalid launch
+  if (input.numel() == 0) return out;
+  const long rows = input.numel() / hidden;
   launch_rmsnorm(out.data_ptr(), res_out_ptr, input.data_ptr(), res_ptr,
                  weight.data_ptr(), (float)eps, (int)rows, hidden,
                  current_stream());
@@ -343,6 +345,9 @@ torch::Tensor skinny_linear_impl(const torch::Tensor& x,
   TORCH_CHECK(M <= 64, "skinny_linear requires M <= 64");
   TORCH_CHECK(K % 128 == 0, "K must be a multiple of 128");
   auto y = torch::empty({M, N}, x.options());
+  // N == 0 is a zero-sized GEMM grid and M == 0 a zero-sized merge grid:
+  // both are invalid launches, and there is nothing to compute
+  if (M == 0 || N == 0) return y;
   const int sk = skinny_gemm_num_splits(N, K, skinny_gemm_tile_n(M));
   torch::Tensor ws;
   void* ws_ptr = nullptr;
@@ -364,6 +369,16 @@ torch::Tensor skinny_linear(torch::Tensor x, torch::Tensor w) {
 torch::Tensor skinny_linear_fp8(torch::Tensor x, torch::Tensor w,
                                 torch::Tensor w_scale) {
   return skinny_linear_impl(x, w, w_scale);
+}
+
+// The split-K factor skinny_linear picks for x [M, K] and w [N, K] (the same
+// for bf16 and fp8 weights); read-only, for tests that mean to exercise one.
+int64_t skinny_linear_splits(int64_t M, int64_t N, int64_t K) {
+  TORCH_CHECK(M >= 0 && M <= 64, "skinny_linear requires M <= 64");
+  TORCH_CHECK(N >= 0 && N < (1L << 31), "N out of range");
+  TORCH_CHECK(K >= 0 && K < (1L << 31) && K % 128 == 0,
+              "K must be a multiple of 128");
+  return skinny_gemm_num_splits((int)N, (int)K, skinny_gemm_tile_n((int)M));
 }
 
 // Operand checks shared by prefill_attn, extend_attn and extend_attn_ragged:
@@ -678,6 +693,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_linear", &skinny_linear,
         "Weight-streaming decode GEMM: x[M,K] @ w[N,K]^T, M <= 64",
         py::arg("x"), py::arg("w"));
+  m.def("skinny_linear_splits", &skinny_linear_splits,
+        "Split-K factor skinny_linear picks for x [M, K] and w [N, K]",
+        py::arg("M"), py::arg("N"), py::arg("K"));
   m.def("moe_route", &moe_route,
         "MoE routing: top-k, softmax weights, expert offsets, sorted slots",
         py::arg("router_logits"), py::arg("top_k"));
