@@ -60,7 +60,7 @@ def main() -> None:
                     ).normal_(0.0, 0.02, generator=gen)
 
                 # advance the stream past the earlier layers' draws
-                # (generator order in _TPLayer: wqkv, wo, w_gate_up,
+                # (generator order in DenseLayer: wqkv, wo, w_gate_up,
                 # w_down per layer)
                 for _ in range(li):
                     w(qs + 2 * ks, h); w(h, qs)

@@ -6,7 +6,9 @@ benchmarks on NVIDIA/MI300X hardware (docs/design/modeling-optimization.md
 step of the target architecture (random-init weights — no network for
 checkpoints) built from this repo's HIP/CDNA4 kernels (wva_amd.ops) with
 GEMMs on hipBLASLt via torch.matmul, used to MEASURE ITL-vs-batch curves
-and KV capacity on the actual GPU.
+and KV capacity on the actual GPU. The layer loop, the attention blocks,
+the layer weights and the KV slab are shared with the Mixtral and TP
+engines and live in calibration/blocks.py.
 
 Single-GPU by design: TP over RCCL/xGMI shards these same GEMMs; the
 autoscaler consumes per-(model, gpuCount) profiles, measured per TP degree
@@ -16,11 +18,12 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import Optional
 
 import torch
 
 from .. import ops
+from . import blocks
 from .paged_kv import BlockAllocator, blocks_for, full_blocks
 
 
@@ -104,20 +107,11 @@ def _quantize_fp8(w: torch.Tensor):
     return w8.contiguous(), scale.contiguous()
 
 
-class _DecoderLayer:
-    def __init__(self, cfg: LlamaConfig, device, dtype, gen):
-        h, std = cfg.hidden_size, 0.02
-        def w(rows, cols):
-            return torch.empty(rows, cols, device=device, dtype=dtype).normal_(
-                0.0, std, generator=gen
-            )
-
-        self.input_norm = torch.ones(h, device=device, dtype=dtype)
-        self.post_attn_norm = torch.ones(h, device=device, dtype=dtype)
-        self.wqkv = w(cfg.q_size + 2 * cfg.kv_size, h)
-        self.wo = w(h, cfg.q_size)
-        self.w_gate_up = w(2 * cfg.intermediate_size, h)
-        self.w_down = w(h, cfg.intermediate_size)
+def _matmul_mlp(layer, h2: torch.Tensor) -> torch.Tensor:
+    """The prefill family's SwiGLU MLP on plain matmuls (ops.linear can
+    divert small M to the skinny kernel under WVA_FORCE_SKINNY)."""
+    act = ops.silu_mul_fused(h2 @ layer.w_gate_up.t())
+    return act @ layer.w_down.t()
 
 
 class LlamaDecodeModel:
@@ -177,19 +171,19 @@ class LlamaDecodeModel:
         gen = torch.Generator(device=self.device)
         gen.manual_seed(seed)
 
-        self.embed = torch.empty(
-            cfg.vocab_size, cfg.hidden_size, device=self.device, dtype=self.dtype
-        ).normal_(0.0, 0.02, generator=gen)
-        self.layers: List[_DecoderLayer] = [
-            _DecoderLayer(cfg, self.device, self.dtype, gen)
+        draw = (self.device, self.dtype, gen)
+        self.embed = blocks.w(cfg.vocab_size, cfg.hidden_size, *draw)
+        self.layers = [
+            blocks.DenseLayer(
+                cfg.hidden_size, cfg.q_size, cfg.kv_size,
+                cfg.intermediate_size, *draw,
+            )
             for _ in range(cfg.num_layers)
         ]
         self.final_norm = torch.ones(
             cfg.hidden_size, device=self.device, dtype=self.dtype
         )
-        self.lm_head = torch.empty(
-            cfg.vocab_size, cfg.hidden_size, device=self.device, dtype=self.dtype
-        ).normal_(0.0, 0.02, generator=gen)
+        self.lm_head = blocks.w(cfg.vocab_size, cfg.hidden_size, *draw)
         if weights_dtype == "fp8":
             for layer in self.layers:
                 for attr in ("wqkv", "wo", "w_gate_up", "w_down"):
@@ -206,17 +200,10 @@ class LlamaDecodeModel:
         if self.paged:
             self._init_paged(block_size, num_gpu_blocks, seed)
             return
-        # Head-major contiguous KV cache per layer: [B, Hk, S, D] — each
-        # (sequence, kv-head) is one sequential HBM stream for the
-        # attention kernel's tile staging (docs/mi355x-kernels.md)
-        self.k_cache = [
-            torch.zeros(
-                max_batch, cfg.num_kv_heads, max_seq, cfg.head_dim,
-                device=self.device, dtype=self.cache_dtype,
-            )
-            for _ in range(cfg.num_layers)
-        ]
-        self.v_cache = [torch.zeros_like(self.k_cache[0]) for _ in range(cfg.num_layers)]
+        self.k_cache, self.v_cache = blocks.alloc_kv_slabs(
+            cfg.num_layers, max_batch, cfg.num_kv_heads, max_seq,
+            cfg.head_dim, self.device, self.cache_dtype,
+        )
 
     # --- paged KV cache ---
 
@@ -334,18 +321,9 @@ class LlamaDecodeModel:
         if headroom is not None or shared_prefix:
             raise ValueError(
                 "headroom and shared_prefix need kv_layout=\"paged\"")
-        self.context_lens.zero_()
-        self.context_lens[:batch] = context_len
-        for layer in range(self.cfg.num_layers):
-            if self.cache_dtype == torch.bfloat16:
-                self.k_cache[layer][:batch, :, :context_len].normal_(0.0, 1.0)
-                self.v_cache[layer][:batch, :, :context_len].normal_(0.0, 1.0)
-            else:  # normal_ unsupported on float8: generate + cast
-                shape = self.k_cache[layer][:batch, :, :context_len].shape
-                for cache in (self.k_cache, self.v_cache):
-                    cache[layer][:batch, :, :context_len] = torch.randn(
-                        shape, device=self.device, dtype=torch.bfloat16
-                    ).to(self.cache_dtype)
+        blocks.reset_kv_slabs(
+            self.context_lens, self.k_cache, self.v_cache, batch, context_len
+        )
 
     def _linear(self, x: torch.Tensor, layer, name: str) -> torch.Tensor:
         """bf16: ops.linear (hipBLASLt); fp8 weights: weight-only W8A16
@@ -387,46 +365,37 @@ class LlamaDecodeModel:
         # launch per step, not per layer — profiling showed 32 redundant
         # int-add launches/step, profiles/decode8b_r2_kernel_stats.txt)
         x = self.embed.index_select(0, token_ids)  # [B, H]
-        residual: Optional[torch.Tensor] = None
+        if self.paged:
+            tables = self.block_tables[:B]
 
-        for li, layer in enumerate(self.layers):
-            if residual is None:
-                residual = x.clone()
-                h = ops.rmsnorm(x, layer.input_norm, None, cfg.rms_eps)
-            else:
-                h = ops.rmsnorm(x, layer.input_norm, residual, cfg.rms_eps)
-
+        def attn(li, layer, h):
             qkv = self._linear(h, layer, "wqkv")
             # fused: RoPE on the strided qkv row + KV-cache append
             if self.paged:
-                tables = self.block_tables[:B]
                 q = ops.rope_append_kv_paged(
                     qkv, self.k_pages[li], self.v_pages[li], tables,
                     positions, cfg.num_q_heads, cfg.num_kv_heads,
                     cfg.rope_theta,
                 )
-                attn = ops.paged_decode_attn(
+                a = ops.paged_decode_attn(
                     q, self.k_pages[li], self.v_pages[li], tables, ctx,
                     self.scale,
-                )
+                ).reshape(B, cfg.q_size)
             else:
-                q = ops.rope_append_kv(
-                    qkv, self.k_cache[li][:B], self.v_cache[li][:B],
-                    positions, cfg.num_q_heads, cfg.num_kv_heads,
-                    cfg.rope_theta,
-                )
-                attn = ops.gqa_decode_attn(
-                    q, self.k_cache[li][:B], self.v_cache[li][:B], ctx,
+                a = blocks.decode_attn(
+                    qkv, self.k_cache[li], self.v_cache[li], positions, ctx,
+                    cfg.num_q_heads, cfg.num_kv_heads, cfg.rope_theta,
                     self.scale,
                 )
-            x = self._linear(attn.reshape(B, cfg.q_size), layer, "wo")
+            return self._linear(a, layer, "wo")
 
-            h2 = ops.rmsnorm(x, layer.post_attn_norm, residual, cfg.rms_eps)
-            gate_up = self._linear(h2, layer, "w_gate_up")
-            act = ops.silu_mul_fused(gate_up)
-            x = self._linear(act, layer, "w_down")
+        def mlp(layer, h2):
+            act = ops.silu_mul_fused(self._linear(h2, layer, "w_gate_up"))
+            return self._linear(act, layer, "w_down")
 
-        final = ops.rmsnorm(x, self.final_norm, residual, cfg.rms_eps)
+        final = blocks.run_layers(
+            self.layers, x, self.final_norm, cfg.rms_eps, attn, mlp
+        )
         logits = self._linear(final, None, "lm_head")
         self.context_lens[:B] += 1
         return logits
@@ -462,87 +431,27 @@ class LlamaDecodeModel:
                 "dequantize every layer per pass)"
             )
         B, S = token_ids.shape
-        T = B * S
         if S > self.max_seq:
             raise ValueError(f"S={S} exceeds max_seq={self.max_seq}")
         positions = (
             torch.arange(S, device=self.device, dtype=torch.int32)
             .repeat(B)
-        )  # [T] per-token position
+        )  # [T = B·S] per-token position
 
         x = self.embed.index_select(0, token_ids.reshape(-1))  # [T, H]
-        residual: Optional[torch.Tensor] = None
+        causal = blocks.causal_mask(S, self.device)
 
-        causal = torch.full(
-            (S, S), float("-inf"), device=self.device, dtype=torch.float32
-        ).triu(1)
-
-        for li, layer in enumerate(self.layers):
-            if residual is None:
-                residual = x.clone()
-                h = ops.rmsnorm(x, layer.input_norm, None, cfg.rms_eps)
-            else:
-                h = ops.rmsnorm(x, layer.input_norm, residual, cfg.rms_eps)
-
+        def attn(li, layer, h):
             qkv = h @ layer.wqkv.t()  # [T, (Hq+2Hk)·D] — prefill M is large
-            q, k, v = qkv.split(
-                [cfg.q_size, cfg.kv_size, cfg.kv_size], dim=-1
+            a = blocks.prefill_attn(
+                qkv, self.k_cache[li], self.v_cache[li], positions, cfg,
+                B, S, self.scale, causal,
             )
-            q = q.reshape(T, cfg.num_q_heads, cfg.head_dim).contiguous()
-            k = k.reshape(T, cfg.num_kv_heads, cfg.head_dim).contiguous()
-            ops.rope(q, k, positions, cfg.rope_theta)  # in-place HIP kernel
-            v = v.reshape(T, cfg.num_kv_heads, cfg.head_dim)
+            return a @ layer.wo.t()
 
-            # append to the head-major cache [B, Hk, S_max, D]
-            k_b = k.reshape(B, S, cfg.num_kv_heads, cfg.head_dim)
-            v_b = v.reshape(B, S, cfg.num_kv_heads, cfg.head_dim)
-            self.k_cache[li][:B, :, :S].copy_(k_b.permute(0, 2, 1, 3))
-            self.v_cache[li][:B, :, :S].copy_(v_b.permute(0, 2, 1, 3))
-
-            if q.is_cuda:
-                # hand-written MFMA flash-prefill kernel (gfx950)
-                attn = ops.prefill_attn(
-                    q, self.k_cache[li], self.v_cache[li], B, S, self.scale
-                ).reshape(T, cfg.q_size)
-            else:
-                # CPU numerics reference: explicit causal matmul attention
-                G = cfg.num_q_heads // cfg.num_kv_heads
-                qh = (
-                    q.reshape(B, S, cfg.num_kv_heads, G, cfg.head_dim)
-                    .permute(0, 2, 3, 1, 4)
-                    .reshape(B * cfg.num_kv_heads * G, S, cfg.head_dim)
-                )
-                kh = (
-                    self.k_cache[li][:B, :, :S].to(self.dtype)
-                    .unsqueeze(2)
-                    .expand(B, cfg.num_kv_heads, G, S, cfg.head_dim)
-                    .reshape(B * cfg.num_kv_heads * G, S, cfg.head_dim)
-                )
-                vh = (
-                    self.v_cache[li][:B, :, :S].to(self.dtype)
-                    .unsqueeze(2)
-                    .expand(B, cfg.num_kv_heads, G, S, cfg.head_dim)
-                    .reshape(B * cfg.num_kv_heads * G, S, cfg.head_dim)
-                )
-                scores = (
-                    torch.bmm(qh, kh.transpose(1, 2)).float() * self.scale
-                    + causal
-                )
-                p = torch.softmax(scores, dim=-1).to(self.dtype)
-                attn = torch.bmm(p, vh)  # [B*Hq, S, D]
-                attn = (
-                    attn.reshape(B, cfg.num_q_heads, S, cfg.head_dim)
-                    .permute(0, 2, 1, 3)
-                    .reshape(T, cfg.q_size)
-                ).contiguous()
-            x = attn @ layer.wo.t()
-
-            h2 = ops.rmsnorm(x, layer.post_attn_norm, residual, cfg.rms_eps)
-            gate_up = h2 @ layer.w_gate_up.t()
-            act = ops.silu_mul_fused(gate_up)
-            x = act @ layer.w_down.t()
-
-        final = ops.rmsnorm(x, self.final_norm, residual, cfg.rms_eps)
+        final = blocks.run_layers(
+            self.layers, x, self.final_norm, cfg.rms_eps, attn, _matmul_mlp
+        )
         last = final.reshape(B, S, cfg.hidden_size)[:, -1].contiguous()
         logits = last @ self.lm_head.t()
         self.context_lens.zero_()
@@ -648,53 +557,33 @@ class LlamaDecodeModel:
 
     def _mixed_layers(self, tokens, Bd, T, positions, chunk_attn):
         """The layer loop of one mixed iteration over `tokens [Bd + T]`:
-        rows 0..Bd-1 decode on cache rows 0..Bd-1 (rope_append_kv +
-        gqa_decode_attn), rows Bd.. are T prefill rows at `positions [T]`
-        whose K/V write and attention are `chunk_attn(li, q, k, v)` (q, k
-        roped [T, H*, D], v [T, Hk, D]) -> [T, Hq, D]. Norms and linears
-        run once over all rows. Returns the final-normed hidden states."""
+        rows 0..Bd-1 decode on cache rows 0..Bd-1 (blocks.decode_attn), rows
+        Bd.. are T prefill rows at `positions [T]` whose K/V write and
+        attention are `chunk_attn(li, q, k, v)` (q, k roped [T, H*, D],
+        v [T, Hk, D]) -> [T, Hq, D]. Norms and linears run once over all
+        rows. Returns the final-normed hidden states."""
         cfg = self.cfg
-        Hq, Hk, D = cfg.num_q_heads, cfg.num_kv_heads, cfg.head_dim
         if Bd:
             d_pos = self.context_lens[:Bd].clone()
             d_ctx = d_pos + 1
         x = self.embed.index_select(0, tokens)  # [Bd + T, H]
-        residual: Optional[torch.Tensor] = None
-        for li, layer in enumerate(self.layers):
-            if residual is None:
-                residual = x.clone()
-                h = ops.rmsnorm(x, layer.input_norm, None, cfg.rms_eps)
-            else:
-                h = ops.rmsnorm(x, layer.input_norm, residual, cfg.rms_eps)
-            qkv = h @ layer.wqkv.t()
 
-            q, k, v = qkv[Bd:].split(
-                [cfg.q_size, cfg.kv_size, cfg.kv_size], dim=-1
-            )
-            q = q.reshape(T, Hq, D).contiguous()
-            k = k.reshape(T, Hk, D).contiguous()
-            ops.rope(q, k, positions, cfg.rope_theta)
-            attn = chunk_attn(li, q, k, v.reshape(T, Hk, D)).reshape(
-                T, cfg.q_size
-            )
+        def attn(li, layer, h):
+            qkv = h @ layer.wqkv.t()
+            q, k, v = blocks.prefill_qkv(qkv[Bd:], positions, cfg)
+            a = chunk_attn(li, q, k, v).reshape(T, cfg.q_size)
             if Bd:
-                qd = ops.rope_append_kv(
-                    qkv[:Bd], self.k_cache[li][:Bd], self.v_cache[li][:Bd],
-                    d_pos, Hq, Hk, cfg.rope_theta,
-                )
-                attn_d = ops.gqa_decode_attn(
-                    qd, self.k_cache[li][:Bd], self.v_cache[li][:Bd], d_ctx,
+                a_d = blocks.decode_attn(
+                    qkv[:Bd], self.k_cache[li], self.v_cache[li], d_pos,
+                    d_ctx, cfg.num_q_heads, cfg.num_kv_heads, cfg.rope_theta,
                     self.scale,
                 )
-                attn = torch.cat([attn_d.reshape(Bd, cfg.q_size), attn])
-            x = attn @ layer.wo.t()
+                a = torch.cat([a_d, a])
+            return a @ layer.wo.t()
 
-            h2 = ops.rmsnorm(x, layer.post_attn_norm, residual, cfg.rms_eps)
-            gate_up = h2 @ layer.w_gate_up.t()
-            act = ops.silu_mul_fused(gate_up)
-            x = act @ layer.w_down.t()
-
-        return ops.rmsnorm(x, self.final_norm, residual, cfg.rms_eps)
+        return blocks.run_layers(
+            self.layers, x, self.final_norm, cfg.rms_eps, attn, _matmul_mlp
+        )
 
     @torch.no_grad()
     def ragged_step(

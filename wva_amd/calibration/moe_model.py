@@ -7,9 +7,10 @@ family the same way calibration/model.py does for dense Llama. Mixtral
 192 GB MI300X needs TP=2), which is itself an MI355X capacity statement
 the cost solver exploits.
 
-Architecture: Llama-style attention (same HIP kernels: fused add-RMSNorm,
-rope_append_kv, GQA decode attention) + top-2 routed expert MLPs. At
-decode batches the expert MLPs run DENSE-batched — one hipBLASLt
+Architecture: Llama-style attention (the layer loop, attention blocks and
+KV slab of calibration/blocks.py, shared with the Llama engines: fused
+add-RMSNorm, rope_append_kv, GQA decode attention) + top-2 routed expert
+MLPs. At decode batches the expert MLPs run DENSE-batched — one hipBLASLt
 strided-batched GEMM pair per layer over all experts (see _moe_mlp) —
 because decode MoE is weight-streaming-bound and the sparse gather path's
 per-expert `nonzero()` syncs dominate. `moe_impl="grouped"` instead routes
@@ -20,51 +21,31 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import List, Optional
 
 import torch
 
 from .. import ops
+from . import blocks
+from .model import LlamaConfig
 
 
 @dataclass
-class MixtralConfig:
+class MixtralConfig(LlamaConfig):
     name: str = "mistralai/Mixtral-8x7B"
-    hidden_size: int = 4096
-    intermediate_size: int = 14336
-    num_layers: int = 32
-    num_q_heads: int = 32
-    num_kv_heads: int = 8
-    head_dim: int = 128
     vocab_size: int = 32000
     rope_theta: float = 1000000.0
-    rms_eps: float = 1e-5
     num_experts: int = 8
     top_k: int = 2
 
-    @property
-    def q_size(self) -> int:
-        return self.num_q_heads * self.head_dim
-
-    @property
-    def kv_size(self) -> int:
-        return self.num_kv_heads * self.head_dim
-
-    def kv_bytes_per_token(self, dtype_bytes: int = 2) -> int:
-        return 2 * self.num_layers * self.kv_size * dtype_bytes
-
     def weight_bytes(self, dtype_bytes: int = 2) -> int:
-        per_layer = (
-            self.hidden_size * (self.q_size + 2 * self.kv_size)
-            + self.q_size * self.hidden_size
-            + self.num_experts * 3 * self.hidden_size * self.intermediate_size
-            + self.hidden_size * self.num_experts  # router
-            + 2 * self.hidden_size
+        # the dense layer's one MLP becomes num_experts of them + a router
+        per_layer_extra = (
+            (self.num_experts - 1) * 3 * self.hidden_size
+            * self.intermediate_size
+            + self.hidden_size * self.num_experts
         )
-        return dtype_bytes * (
-            self.num_layers * per_layer
-            + 2 * self.vocab_size * self.hidden_size
-            + self.hidden_size
+        return super().weight_bytes(dtype_bytes) + (
+            dtype_bytes * self.num_layers * per_layer_extra
         )
 
 
@@ -83,49 +64,38 @@ TINY_MOE = MixtralConfig(
 )
 
 
-class _MoELayer:
+class _MoELayer(blocks.AttnLayer):
     def __init__(self, cfg: MixtralConfig, device, dtype, gen):
-        h, std = cfg.hidden_size, 0.02
+        h, inter = cfg.hidden_size, cfg.intermediate_size
+        super().__init__(h, cfg.q_size, cfg.kv_size, device, dtype, gen)
+        self.w_router = blocks.w(cfg.num_experts, h, device, dtype, gen)
+        self.set_expert_weights(
+            torch.stack([
+                blocks.w(2 * inter, h, device, dtype, gen)
+                for _ in range(cfg.num_experts)
+            ]),
+            torch.stack([
+                blocks.w(h, inter, device, dtype, gen)
+                for _ in range(cfg.num_experts)
+            ]),
+        )
 
-        def w(rows, cols):
-            return torch.empty(rows, cols, device=device, dtype=dtype).normal_(
-                0.0, std, generator=gen
-            )
-
-        self.input_norm = torch.ones(h, device=device, dtype=dtype)
-        self.post_attn_norm = torch.ones(h, device=device, dtype=dtype)
-        self.wqkv = w(cfg.q_size + 2 * cfg.kv_size, h)
-        self.wo = w(h, cfg.q_size)
-        self.w_router = w(cfg.num_experts, h)
+    def set_expert_weights(self, gate_up_stacked, down_stacked) -> None:
+        """Replace expert weights, recomputing every derived operand
+        (tests copy weights between devices through this)."""
         # experts as STACKED tensors [E, 2I, H] / [E, H, I]: the decode
         # path runs them as one strided-batched GEMM pair per layer (see
         # MixtralDecodeModel._moe_mlp); per-expert views kept for the
         # sparse reference path
-        self.w_gate_up_stacked = torch.stack(
-            [w(2 * cfg.intermediate_size, h) for _ in range(cfg.num_experts)]
-        )
-        self.w_down_stacked = torch.stack(
-            [w(h, cfg.intermediate_size) for _ in range(cfg.num_experts)]
-        )
-        self.w_gate_up = list(self.w_gate_up_stacked)
-        self.w_down = list(self.w_down_stacked)
+        self.w_gate_up_stacked = gate_up_stacked
+        self.w_down_stacked = down_stacked
+        self.w_gate_up = list(gate_up_stacked)
+        self.w_down = list(down_stacked)
         # dense-path operands (no transposed VIEWS at run time — hipBLASLt
         # takes a catastrophically slow route for strided-batched GEMMs on
         # transposed views of these shapes; measured 11 ms/layer):
         #  * gate_up runs as ONE flat GEMM against [E·2I, H] (a free view)
         #  * down runs as bmm against a pre-transposed CONTIGUOUS [E, I, H]
-        self.w_gate_up_flat = self.w_gate_up_stacked.reshape(
-            cfg.num_experts * 2 * cfg.intermediate_size, h
-        )
-        self.w_down_t = self.w_down_stacked.transpose(1, 2).contiguous()
-
-    def set_expert_weights(self, gate_up_stacked, down_stacked) -> None:
-        """Replace expert weights, recomputing every derived operand
-        (tests copy weights between devices through this)."""
-        self.w_gate_up_stacked = gate_up_stacked
-        self.w_down_stacked = down_stacked
-        self.w_gate_up = list(gate_up_stacked)
-        self.w_down = list(down_stacked)
         e2i, h = (
             gate_up_stacked.shape[0] * gate_up_stacked.shape[1],
             gate_up_stacked.shape[2],
@@ -144,7 +114,8 @@ MOE_IMPLS = ("auto", "dense", "sparse", "grouped")
 
 
 class MixtralDecodeModel:
-    """Decode-only MoE engine; same KV-cache layout as LlamaDecodeModel."""
+    """Mixtral decode and one-shot prefill engine over the contiguous KV
+    slab (blocks.alloc_kv_slabs)."""
 
     def __init__(
         self,
@@ -173,48 +144,27 @@ class MixtralDecodeModel:
         gen = torch.Generator(device=self.device)
         gen.manual_seed(seed)
 
-        self.embed = torch.empty(
-            cfg.vocab_size, cfg.hidden_size, device=self.device, dtype=self.dtype
-        ).normal_(0.0, 0.02, generator=gen)
-        self.layers: List[_MoELayer] = [
-            _MoELayer(cfg, self.device, self.dtype, gen)
-            for _ in range(cfg.num_layers)
-        ]
+        draw = (self.device, self.dtype, gen)
+        self.embed = blocks.w(cfg.vocab_size, cfg.hidden_size, *draw)
+        self.layers = [_MoELayer(cfg, *draw) for _ in range(cfg.num_layers)]
         self.final_norm = torch.ones(
             cfg.hidden_size, device=self.device, dtype=self.dtype
         )
-        self.lm_head = torch.empty(
-            cfg.vocab_size, cfg.hidden_size, device=self.device, dtype=self.dtype
-        ).normal_(0.0, 0.02, generator=gen)
+        self.lm_head = blocks.w(cfg.vocab_size, cfg.hidden_size, *draw)
 
-        self.k_cache = [
-            torch.zeros(
-                max_batch, cfg.num_kv_heads, max_seq, cfg.head_dim,
-                device=self.device, dtype=self.cache_dtype,
-            )
-            for _ in range(cfg.num_layers)
-        ]
-        self.v_cache = [
-            torch.zeros_like(self.k_cache[0]) for _ in range(cfg.num_layers)
-        ]
+        self.k_cache, self.v_cache = blocks.alloc_kv_slabs(
+            cfg.num_layers, max_batch, cfg.num_kv_heads, max_seq,
+            cfg.head_dim, self.device, self.cache_dtype,
+        )
         self.context_lens = torch.zeros(
             max_batch, dtype=torch.int32, device=self.device
         )
         self.scale = 1.0 / math.sqrt(cfg.head_dim)
 
     def reset(self, batch: int, context_len: int) -> None:
-        self.context_lens.zero_()
-        self.context_lens[:batch] = context_len
-        for layer in range(self.cfg.num_layers):
-            if self.cache_dtype == torch.bfloat16:
-                self.k_cache[layer][:batch, :, :context_len].normal_(0.0, 1.0)
-                self.v_cache[layer][:batch, :, :context_len].normal_(0.0, 1.0)
-            else:  # normal_ unsupported on float8: generate + cast
-                shape = self.k_cache[layer][:batch, :, :context_len].shape
-                for cache in (self.k_cache, self.v_cache):
-                    cache[layer][:batch, :, :context_len] = torch.randn(
-                        shape, device=self.device, dtype=torch.bfloat16
-                    ).to(self.cache_dtype)
+        blocks.reset_kv_slabs(
+            self.context_lens, self.k_cache, self.v_cache, batch, context_len
+        )
 
     def _moe_mlp(self, layer: _MoELayer, h2: torch.Tensor) -> torch.Tensor:
         """MoE MLP; dense-batched for decode batches (B ≤ 64).
@@ -297,29 +247,18 @@ class MixtralDecodeModel:
         ctx = positions + 1  # hoisted out of the layer loop
 
         x = self.embed.index_select(0, token_ids)
-        residual: Optional[torch.Tensor] = None
 
-        for li, layer in enumerate(self.layers):
-            if residual is None:
-                residual = x.clone()
-                h = ops.rmsnorm(x, layer.input_norm, None, cfg.rms_eps)
-            else:
-                h = ops.rmsnorm(x, layer.input_norm, residual, cfg.rms_eps)
-
-            qkv = ops.linear(h, layer.wqkv)
-            q = ops.rope_append_kv(
-                qkv, self.k_cache[li][:B], self.v_cache[li][:B],
-                positions, cfg.num_q_heads, cfg.num_kv_heads, cfg.rope_theta,
+        def attn(li, layer, h):
+            a = blocks.decode_attn(
+                ops.linear(h, layer.wqkv), self.k_cache[li], self.v_cache[li],
+                positions, ctx, cfg.num_q_heads, cfg.num_kv_heads,
+                cfg.rope_theta, self.scale,
             )
-            attn = ops.gqa_decode_attn(
-                q, self.k_cache[li][:B], self.v_cache[li][:B], ctx, self.scale
-            )
-            x = ops.linear(attn.reshape(B, cfg.q_size), layer.wo)
+            return ops.linear(a, layer.wo)
 
-            h2 = ops.rmsnorm(x, layer.post_attn_norm, residual, cfg.rms_eps)
-            x = self._moe_mlp(layer, h2)
-
-        final = ops.rmsnorm(x, self.final_norm, residual, cfg.rms_eps)
+        final = blocks.run_layers(
+            self.layers, x, self.final_norm, cfg.rms_eps, attn, self._moe_mlp
+        )
         logits = ops.linear(final, self.lm_head)
         self.context_lens[:B] += 1
         return logits
@@ -338,7 +277,6 @@ class MixtralDecodeModel:
         """
         cfg = self.cfg
         B, S = token_ids.shape
-        T = B * S
         if S > self.max_seq:
             raise ValueError(f"S={S} exceeds max_seq={self.max_seq}")
         positions = (
@@ -346,70 +284,21 @@ class MixtralDecodeModel:
         )
 
         x = self.embed.index_select(0, token_ids.reshape(-1))
-        residual = None
-        causal = None
-        if not x.is_cuda:
-            causal = torch.full(
-                (S, S), float("-inf"), device=self.device, dtype=torch.float32
-            ).triu(1)
+        causal = None if x.is_cuda else blocks.causal_mask(S, self.device)
 
-        for li, layer in enumerate(self.layers):
-            if residual is None:
-                residual = x.clone()
-                h = ops.rmsnorm(x, layer.input_norm, None, cfg.rms_eps)
-            else:
-                h = ops.rmsnorm(x, layer.input_norm, residual, cfg.rms_eps)
+        def attn(li, layer, h):
+            a = blocks.prefill_attn(
+                h @ layer.wqkv.t(), self.k_cache[li], self.v_cache[li],
+                positions, cfg, B, S, self.scale, causal,
+            )
+            return a @ layer.wo.t()
 
-            qkv = h @ layer.wqkv.t()
-            q, k, v = qkv.split([cfg.q_size, cfg.kv_size, cfg.kv_size], dim=-1)
-            q = q.reshape(T, cfg.num_q_heads, cfg.head_dim).contiguous()
-            k = k.reshape(T, cfg.num_kv_heads, cfg.head_dim).contiguous()
-            ops.rope(q, k, positions, cfg.rope_theta)
-            k_b = k.reshape(B, S, cfg.num_kv_heads, cfg.head_dim)
-            v_b = v.reshape(B, S, cfg.num_kv_heads, cfg.head_dim)
-            self.k_cache[li][:B, :, :S].copy_(k_b.permute(0, 2, 1, 3))
-            self.v_cache[li][:B, :, :S].copy_(v_b.permute(0, 2, 1, 3))
+        def mlp(layer, h2):
+            return self._moe_mlp_impl(layer, h2, dense=False)
 
-            if q.is_cuda:
-                attn = ops.prefill_attn(
-                    q, self.k_cache[li], self.v_cache[li], B, S, self.scale
-                ).reshape(T, cfg.q_size)
-            else:
-                G = cfg.num_q_heads // cfg.num_kv_heads
-                qh = (
-                    q.reshape(B, S, cfg.num_kv_heads, G, cfg.head_dim)
-                    .permute(0, 2, 3, 1, 4)
-                    .reshape(B * cfg.num_kv_heads * G, S, cfg.head_dim)
-                )
-                kh = (
-                    self.k_cache[li][:B, :, :S].to(self.dtype)
-                    .unsqueeze(2)
-                    .expand(B, cfg.num_kv_heads, G, S, cfg.head_dim)
-                    .reshape(B * cfg.num_kv_heads * G, S, cfg.head_dim)
-                )
-                vh = (
-                    self.v_cache[li][:B, :, :S].to(self.dtype)
-                    .unsqueeze(2)
-                    .expand(B, cfg.num_kv_heads, G, S, cfg.head_dim)
-                    .reshape(B * cfg.num_kv_heads * G, S, cfg.head_dim)
-                )
-                scores = (
-                    torch.bmm(qh, kh.transpose(1, 2)).float() * self.scale
-                    + causal
-                )
-                p = torch.softmax(scores, dim=-1).to(self.dtype)
-                attn = torch.bmm(p, vh)
-                attn = (
-                    attn.reshape(B, cfg.num_q_heads, S, cfg.head_dim)
-                    .permute(0, 2, 1, 3)
-                    .reshape(T, cfg.q_size)
-                ).contiguous()
-            x = attn @ layer.wo.t()
-
-            h2 = ops.rmsnorm(x, layer.post_attn_norm, residual, cfg.rms_eps)
-            x = self._moe_mlp_impl(layer, h2, dense=False)
-
-        final = ops.rmsnorm(x, self.final_norm, residual, cfg.rms_eps)
+        final = blocks.run_layers(
+            self.layers, x, self.final_norm, cfg.rms_eps, attn, mlp
+        )
         last = final.reshape(B, S, cfg.hidden_size)[:, -1].contiguous()
         logits = last @ self.lm_head.t()
         self.context_lens.zero_()

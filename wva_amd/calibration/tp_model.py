@@ -15,6 +15,9 @@ Sharding (standard column/row parallel):
   * Attention + KV cache: local to the rank's heads.
   * Embedding/lm_head replicated (calibration-scale simplification).
 
+The layer weights, KV slab, layer loop and decode attention block are the
+single-GPU engine's (calibration/blocks.py), given this rank's shard sizes.
+
 Run per-TP calibration on an 8-GPU node with:
   torchrun --standalone --local-addr 127.0.0.1 --nproc-per-node N \
       scripts/calibrate_tp.py --model 8b
@@ -22,34 +25,14 @@ Run per-TP calibration on an 8-GPU node with:
 from __future__ import annotations
 
 import math
-from typing import List, Optional
+from typing import Optional
 
 import torch
 import torch.distributed as dist
 
 from .. import ops
+from . import blocks
 from .model import LlamaConfig
-
-
-class _TPLayer:
-    def __init__(self, cfg: LlamaConfig, shard: "TPShardInfo", device, dtype, gen):
-        h, std = cfg.hidden_size, 0.02
-
-        def w(rows, cols):
-            return torch.empty(rows, cols, device=device, dtype=dtype).normal_(
-                0.0, std, generator=gen
-            )
-
-        self.input_norm = torch.ones(h, device=device, dtype=dtype)
-        self.post_attn_norm = torch.ones(h, device=device, dtype=dtype)
-        # column-parallel qkv: this rank's heads only
-        self.wqkv = w(shard.q_size + 2 * shard.kv_size, h)
-        # row-parallel o: [H, q_size/N]
-        self.wo = w(h, shard.q_size)
-        # column-parallel gate_up: [2*I/N, H]
-        self.w_gate_up = w(2 * shard.inter, h)
-        # row-parallel down: [H, I/N]
-        self.w_down = w(h, shard.inter)
 
 
 class TPShardInfo:
@@ -100,32 +83,27 @@ class TPLlamaDecodeModel:
         # same seed on every rank for the replicated parts; shard-unique
         # seed for the sharded weights
         gen.manual_seed(seed)
-        self.embed = torch.empty(
-            cfg.vocab_size, cfg.hidden_size, device=self.device, dtype=self.dtype
-        ).normal_(0.0, 0.02, generator=gen)
+        draw = (self.device, self.dtype, gen)
+        self.embed = blocks.w(cfg.vocab_size, cfg.hidden_size, *draw)
         gen.manual_seed(seed * 1000 + self.rank + 1)
-        self.layers: List[_TPLayer] = [
-            _TPLayer(cfg, self.shard, self.device, self.dtype, gen)
+        shard = self.shard
+        self.layers = [
+            blocks.DenseLayer(
+                cfg.hidden_size, shard.q_size, shard.kv_size, shard.inter,
+                *draw,
+            )
             for _ in range(cfg.num_layers)
         ]
         self.final_norm = torch.ones(
             cfg.hidden_size, device=self.device, dtype=self.dtype
         )
         gen.manual_seed(seed)
-        self.lm_head = torch.empty(
-            cfg.vocab_size, cfg.hidden_size, device=self.device, dtype=self.dtype
-        ).normal_(0.0, 0.02, generator=gen)
+        self.lm_head = blocks.w(cfg.vocab_size, cfg.hidden_size, *draw)
 
-        self.k_cache = [
-            torch.zeros(
-                max_batch, self.shard.num_kv_heads, max_seq, cfg.head_dim,
-                device=self.device, dtype=self.cache_dtype,
-            )
-            for _ in range(cfg.num_layers)
-        ]
-        self.v_cache = [
-            torch.zeros_like(self.k_cache[0]) for _ in range(cfg.num_layers)
-        ]
+        self.k_cache, self.v_cache = blocks.alloc_kv_slabs(
+            cfg.num_layers, max_batch, shard.num_kv_heads, max_seq,
+            cfg.head_dim, self.device, self.cache_dtype,
+        )
         self.context_lens = torch.zeros(
             max_batch, dtype=torch.int32, device=self.device
         )
@@ -137,18 +115,9 @@ class TPLlamaDecodeModel:
         return x
 
     def reset(self, batch: int, context_len: int) -> None:
-        self.context_lens.zero_()
-        self.context_lens[:batch] = context_len
-        for layer in range(self.cfg.num_layers):
-            if self.cache_dtype == torch.bfloat16:
-                self.k_cache[layer][:batch, :, :context_len].normal_(0.0, 1.0)
-                self.v_cache[layer][:batch, :, :context_len].normal_(0.0, 1.0)
-            else:  # normal_ unsupported on float8: generate + cast
-                shape = self.k_cache[layer][:batch, :, :context_len].shape
-                for cache in (self.k_cache, self.v_cache):
-                    cache[layer][:batch, :, :context_len] = torch.randn(
-                        shape, device=self.device, dtype=torch.bfloat16
-                    ).to(self.cache_dtype)
+        blocks.reset_kv_slabs(
+            self.context_lens, self.k_cache, self.v_cache, batch, context_len
+        )
 
     @torch.no_grad()
     def decode_step(self, token_ids: torch.Tensor) -> torch.Tensor:
@@ -160,33 +129,24 @@ class TPLlamaDecodeModel:
         # launch per step, not per layer — profiling showed 32 redundant
         # int-add launches/step, profiles/decode8b_r2_kernel_stats.txt)
         x = self.embed.index_select(0, token_ids)
-        residual: Optional[torch.Tensor] = None
 
-        for li, layer in enumerate(self.layers):
-            if residual is None:
-                residual = x.clone()
-                h = ops.rmsnorm(x, layer.input_norm, None, cfg.rms_eps)
-            else:
-                h = ops.rmsnorm(x, layer.input_norm, residual, cfg.rms_eps)
-
-            qkv = ops.linear(h, layer.wqkv)  # local heads only
-            q = ops.rope_append_kv(
-                qkv, self.k_cache[li][:B], self.v_cache[li][:B],
-                positions, shard.num_q_heads, shard.num_kv_heads,
-                cfg.rope_theta,
-            )
-            attn = ops.gqa_decode_attn(
-                q, self.k_cache[li][:B], self.v_cache[li][:B], ctx, self.scale
+        def attn(li, layer, h):
+            a = blocks.decode_attn(
+                ops.linear(h, layer.wqkv),  # local heads only
+                self.k_cache[li], self.v_cache[li], positions, ctx,
+                shard.num_q_heads, shard.num_kv_heads, cfg.rope_theta,
+                self.scale,
             )
             # row-parallel o-proj: partials all-reduced over RCCL/xGMI
-            x = self._all_reduce(ops.linear(attn.reshape(B, shard.q_size), layer.wo))
+            return self._all_reduce(ops.linear(a, layer.wo))
 
-            h2 = ops.rmsnorm(x, layer.post_attn_norm, residual, cfg.rms_eps)
-            gate_up = ops.linear(h2, layer.w_gate_up)
-            act = ops.silu_mul_fused(gate_up)
-            x = self._all_reduce(ops.linear(act, layer.w_down))
+        def mlp(layer, h2):
+            act = ops.silu_mul_fused(ops.linear(h2, layer.w_gate_up))
+            return self._all_reduce(ops.linear(act, layer.w_down))
 
-        final = ops.rmsnorm(x, self.final_norm, residual, cfg.rms_eps)
+        final = blocks.run_layers(
+            self.layers, x, self.final_norm, cfg.rms_eps, attn, mlp
+        )
         logits = ops.linear(final, self.lm_head)
         self.context_lens[:B] += 1
         return logits

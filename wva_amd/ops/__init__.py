@@ -699,8 +699,8 @@ def prefill_attn(
 ) -> torch.Tensor:
     """Causal GQA flash-prefill over the (populated) head-major caches.
 
-    GPU-only (fail-loud): the CPU prefill reference lives in
-    calibration/model.py's matmul branch.
+    GPU-only (fail-loud): the CPU prefill reference is
+    calibration/blocks.py's causal_attn_reference.
     """
     return _require_ext().prefill_attn(q, k_cache, v_cache, batch, seq, scale)
 
