@@ -124,8 +124,9 @@ class LlamaDecodeModel:
       and one block table [max_batch, max_seq / block_size] shared by all
       layers (vLLM's num_gpu_blocks x block_size layout). `num_gpu_blocks`
       defaults to max_batch * max_seq / block_size, the slab's bytes; a
-      smaller pool holds many short sequences. Decode path only: the
-      prefill-family methods raise NotImplementedError.
+      smaller pool holds many short sequences. It has the decode path and
+      `paged_ragged_step` (mixed decode / chunked prefill over pages); the
+      five contiguous prefill-family methods raise NotImplementedError.
     """
 
     def __init__(
@@ -654,6 +655,97 @@ class LlamaDecodeModel:
             )
 
         final = self._mixed_layers(tokens, Bd, T, positions, chunk_attn)
+        last = final[Bd:].index_select(0, (ends - 1).clamp_(0, T - 1))
+        logits = torch.cat([final[:Bd], last]) @ self.lm_head.t()
+        self.context_lens[:Bd] += 1
+        self.context_lens[Bd:Bd + Bp] += lens
+        return logits
+
+    @torch.no_grad()
+    def paged_ragged_step(
+        self,
+        decode_tokens: Optional[torch.Tensor],
+        chunk_tokens: torch.Tensor,
+        chunk_lens: torch.Tensor,
+        max_chunk: int,
+    ) -> torch.Tensor:
+        """`ragged_step` on the paged layout (and only there: a contiguous
+        engine raises ValueError): sequences 0..Bd-1 decode one token each,
+        sequences Bd..Bd+Bp-1 each continue by chunk_lens[b] tokens from their
+        own context_lens, with the operands, the returned logits
+        [Bd+Bp, vocab] and the context_lens update of `ragged_step`.
+
+        Per layer one qkv GEMM covers all Bd + T rows. The decode rows go
+        through rope_append_kv_paged and paged_decode_attn on
+        block_tables[:Bd]; the chunk rows through one
+        rope_append_kv_chunk_paged (RoPE and the K/V write of every chunk,
+        positions formed in the kernel: no searchsorted, no row gather and
+        no indexed write) and one extend_attn_ragged_paged on
+        block_tables[Bd:Bd+Bp]; then one wo GEMM and the MLP.
+
+        Pages come from the caller's `reset(batch, context_len,
+        headroom=...)` reservation and nothing is allocated here: the caller
+        keeps context_lens[b] + chunk_lens[b] (and + 1 for a decode row)
+        inside it. A chunk that runs past its reservation loses the K/V rows
+        that have no page (the store rule of the append kernels) and later
+        steps attend to whatever the clamped table entries point at: wrong
+        numbers, no bad access. A one-shot prefill over pages is this method
+        from `reset(B, 0, headroom=S)` with `decode_tokens=None`."""
+        if not self.paged:
+            raise ValueError(
+                "paged_ragged_step needs kv_layout=\"paged\"; the contiguous "
+                "layout has ragged_step")
+        if self.weights_dtype != "bf16":
+            raise NotImplementedError(
+                "chunked prefill with fp8 weights is not implemented"
+            )
+        cfg = self.cfg
+        Bd = 0 if decode_tokens is None else decode_tokens.shape[0]
+        Bp, T = chunk_lens.shape[0], chunk_tokens.shape[0]
+        if max_chunk < 1 or max_chunk > self.max_seq:
+            raise ValueError(
+                f"max_chunk={max_chunk}, max_seq={self.max_seq}")
+        if Bp < 1 or T < 1:
+            raise ValueError(
+                "paged_ragged_step needs a chunk sequence and a row")
+        if Bd + Bp > self.max_batch:
+            raise ValueError(f"{Bd}+{Bp} sequences, max_batch={self.max_batch}")
+
+        lens = chunk_lens.to(torch.int32).clamp(0, max_chunk)
+        ends = torch.cumsum(lens, 0)
+        prefix = self.context_lens[Bd:Bd + Bp].clone()  # [Bp] int32
+        p_tables = self.block_tables[Bd:Bd + Bp]
+        tokens = chunk_tokens
+        if Bd:
+            tokens = torch.cat([decode_tokens, tokens])
+            d_pos = self.context_lens[:Bd].clone()
+            d_ctx = d_pos + 1
+            d_tables = self.block_tables[:Bd]
+        x = self.embed.index_select(0, tokens)  # [Bd + T, H]
+        heads = (cfg.num_q_heads, cfg.num_kv_heads, cfg.rope_theta)
+
+        def attn(li, layer, h):
+            qkv = h @ layer.wqkv.t()
+            kp, vp = self.k_pages[li], self.v_pages[li]
+            q = ops.rope_append_kv_chunk_paged(
+                qkv[Bd:], kp, vp, p_tables, prefix, lens, max_chunk, *heads
+            )
+            a = ops.extend_attn_ragged_paged(
+                q, kp, vp, p_tables, prefix, lens, max_chunk, self.scale
+            ).reshape(T, cfg.q_size)
+            if Bd:
+                q_d = ops.rope_append_kv_paged(
+                    qkv[:Bd], kp, vp, d_tables, d_pos, *heads
+                )
+                a_d = ops.paged_decode_attn(
+                    q_d, kp, vp, d_tables, d_ctx, self.scale
+                ).reshape(Bd, cfg.q_size)
+                a = torch.cat([a_d, a])
+            return a @ layer.wo.t()
+
+        final = blocks.run_layers(
+            self.layers, x, self.final_norm, cfg.rms_eps, attn, _matmul_mlp
+        )
         last = final[Bd:].index_select(0, (ends - 1).clamp_(0, T - 1))
         logits = torch.cat([final[:Bd], last]) @ self.lm_head.t()
         self.context_lens[:Bd] += 1

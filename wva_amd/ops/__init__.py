@@ -750,8 +750,7 @@ def extend_attn_ragged(
             num_splits = extend_attn_ragged_num_splits(
                 chunk_lens.shape[0], q.shape[1], max_chunk, k_cache.shape[2]
             )
-        lens = chunk_lens.to(torch.int32)
-        q_starts = torch.cumsum(lens, 0, dtype=torch.int32) - lens
+        lens, q_starts = _ragged_starts(chunk_lens)
         return _require_ext().extend_attn_ragged(
             q, k_cache, v_cache, prefix_lens.to(torch.int32), q_starts, lens,
             max_chunk, scale, num_splits,
@@ -759,6 +758,115 @@ def extend_attn_ragged(
     return extend_attn_ragged_ref(
         q, k_cache, v_cache, prefix_lens, chunk_lens, max_chunk, scale
     ).to(q.dtype)
+
+
+def _ragged_starts(chunk_lens: torch.Tensor):
+    """(lens int32, q_starts int32): the exclusive cumsum of chunk_lens,
+    formed on the tensor's own device."""
+    lens = chunk_lens.to(torch.int32)
+    return lens, torch.cumsum(lens, 0, dtype=torch.int32) - lens
+
+
+def extend_attn_ragged_paged(
+    q: torch.Tensor,
+    k_pages: torch.Tensor,
+    v_pages: torch.Tensor,
+    block_tables: torch.Tensor,
+    prefix_lens: torch.Tensor,
+    chunk_lens: torch.Tensor,
+    max_chunk: int,
+    scale: float,
+    num_splits: Optional[int] = None,
+) -> torch.Tensor:
+    """extend_attn_ragged over a paged KV pool: k_pages / v_pages are
+    [num_blocks, Hk, block_size, 128] (bf16 or float8_e4m3fn, block_size 16,
+    32 or 64) and block_tables [B, max_blocks] int32 maps sequence b's block
+    i to a physical page; the cache size is max_blocks * block_size. The
+    chunk's own K/V rows are already in the pool (rope_append_kv_chunk_paged).
+
+    The live rows of sequence b end at min(prefix_lens[b] + chunk_lens[b],
+    max_blocks * block_size); table entries past them are never looked at and
+    an id outside [0, num_blocks) is clamped into the pool, so a corrupt
+    table gives wrong numbers, never an out-of-bounds access. Only addresses
+    differ from extend_attn_ragged: on the same rows and split count the
+    output is bit-equal to it on the gathered cache. Everything per-sequence
+    stays on the device (graph-capturable)."""
+    if q.is_cuda:
+        if num_splits is None:
+            num_splits = extend_attn_ragged_num_splits(
+                chunk_lens.shape[0], q.shape[1], max_chunk,
+                block_tables.shape[1] * k_pages.shape[2],
+            )
+        lens, q_starts = _ragged_starts(chunk_lens)
+        return _require_ext().extend_attn_ragged_paged(
+            q, k_pages, v_pages, block_tables.to(torch.int32),
+            prefix_lens.to(torch.int32), q_starts, lens, max_chunk, scale,
+            num_splits,
+        )
+    max_seq = block_tables.shape[1] * k_pages.shape[2]
+    prefix = prefix_lens.clamp(0, max_seq)
+    live = (prefix + chunk_lens.clamp(0, max_chunk)).clamp(max=max_seq)
+    return extend_attn_ragged_ref(
+        q,
+        gather_pages(k_pages, block_tables, live),
+        gather_pages(v_pages, block_tables, live),
+        prefix, chunk_lens, max_chunk, scale,
+    ).to(q.dtype)
+
+
+def rope_append_kv_chunk_paged(
+    qkv: torch.Tensor,
+    k_pages: torch.Tensor,
+    v_pages: torch.Tensor,
+    block_tables: torch.Tensor,
+    prefix_lens: torch.Tensor,
+    chunk_lens: torch.Tensor,
+    max_chunk: int,
+    num_q_heads: int,
+    num_kv_heads: int,
+    theta: float = 500000.0,
+) -> torch.Tensor:
+    """The append of ragged chunked prefill into a paged pool, one launch
+    for all in-flight chunks: qkv [T, (Hq+2Hk)*128] packs the chunks' rows
+    as extend_attn_ragged packs q (sequence b owns the chunk_lens[b] <=
+    max_chunk rows from the exclusive cumsum of chunk_lens), and row i of
+    sequence b sits at position prefix_lens[b] + i. Returns RoPE'd q
+    [T, Hq, 128] and stores the rotated K and raw V rows to page
+    block_tables[b, pos // block_size], row pos % block_size. A row whose
+    pos // block_size is past the table, or whose table entry is outside
+    [0, num_blocks), skips its K/V stores and still gets its q. Rows of q
+    that no sequence owns are unspecified. qkv may be a row range of a larger
+    tensor; nothing is read back (graph-capturable)."""
+    if qkv.is_cuda:
+        lens, q_starts = _ragged_starts(chunk_lens)
+        return _require_ext().rope_append_kv_chunk_paged(
+            qkv, k_pages, v_pages, block_tables.to(torch.int32),
+            prefix_lens.to(torch.int32), q_starts, lens, max_chunk,
+            num_q_heads, num_kv_heads, theta,
+        )
+    num_blocks, _, bs, D = k_pages.shape
+    T, max_blocks = qkv.shape[0], block_tables.shape[1]
+    # per-row sequence and position; rows that no sequence owns keep -1
+    seq = torch.zeros(T, dtype=torch.long)
+    pos = torch.full((T,), -1, dtype=torch.long)
+    start = 0
+    for b, n in enumerate(chunk_lens.tolist()):
+        n = min(max(int(n), 0), max_chunk, T - start)
+        p0 = min(max(int(prefix_lens[b]), 0), max_blocks * bs)
+        seq[start:start + n] = b
+        pos[start:start + n] = p0 + torch.arange(n)
+        start += n
+    q, k, v = _rope_split_qkv(
+        qkv, D, pos.clamp(min=0), num_q_heads, num_kv_heads, theta
+    )
+    entry = torch.div(pos, bs, rounding_mode="floor")
+    in_table = (pos >= 0) & (entry < max_blocks)
+    ids = block_tables.long()[seq, entry.clamp(0, max_blocks - 1)]
+    ok = in_table & (ids >= 0) & (ids < num_blocks)
+    ids, rows = ids[ok], (pos % bs)[ok]
+    _as_bytes(k_pages)[ids, :, rows] = _as_bytes(k.to(k_pages.dtype))[ok]
+    _as_bytes(v_pages)[ids, :, rows] = _as_bytes(v.to(v_pages.dtype))[ok]
+    return q
 
 
 def extend_attn_ragged_num_splits(

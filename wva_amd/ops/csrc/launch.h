@@ -45,6 +45,22 @@ void launch_rope_append_kv(const void* qkv, void* q_out, void* k_cache,
                            const PagedKV* paged, int batch, int num_q_heads,
                            int num_kv_heads, int head_dim, int max_seq,
                            float theta, int kv_fp8, hipStream_t stream);
+// Chunk append of ragged chunked prefill: row i < chunk_lens[b] of sequence b
+// is packed row q_starts[b] + i of qkv [total_rows, (Hq + 2·Hk)·128] at
+// position prefix_lens[b] + i. Writes RoPE'd q_out [total_rows, Hq, 128]
+// (rows that no sequence owns are unspecified: the kernel does not write
+// them) and stores rotated k and raw v into the pool through `paged`, which
+// must be non-null for now: a contiguous instantiation is out of scope. A
+// row without a page (see paged_row_offset in rope.hip) skips its K/V
+// stores. grid = (ceil(max_chunk / 4), batch); prefix_lens, q_starts and
+// chunk_lens [batch] stay on the device.
+void launch_rope_append_kv_chunk(const void* qkv, void* q_out, void* k_cache,
+                                 void* v_cache, const int* prefix_lens,
+                                 const int* q_starts, const int* chunk_lens,
+                                 const PagedKV* paged, int batch,
+                                 int total_rows, int max_chunk,
+                                 int num_q_heads, int num_kv_heads,
+                                 float theta, int kv_fp8, hipStream_t stream);
 
 // --- silu_mul.hip ---
 // out = silu(gate) * up over n elements, n even.
@@ -88,14 +104,17 @@ int extend_attn_ragged_num_splits(int batch, int num_q_heads, int max_chunk,
 // rows of q/out [total_rows, Hq, 128] from q_starts[b]; grid = (batch·Hq,
 // ceil(max_chunk/64), num_splits), then the merge when the sweep was split.
 // `ws` holds batch·Hq·ceil(max_chunk/64)·64·num_splits·(2+128) floats and may
-// be null when num_splits == 1. Nothing is read back: graph-capturable.
+// be null when num_splits == 1. Nothing is read back: graph-capturable. With
+// `paged` the caches are a pool (see PagedKV) and the kernels see max_blocks ·
+// block_size as max_seq; workspace and merge are the same.
 void launch_extend_attn_ragged(void* out, void* ws, const void* q,
                                const void* k_cache, const void* v_cache,
                                const int* prefix_lens, const int* q_starts,
                                const int* chunk_lens, int batch,
                                int total_rows, int max_chunk, int num_q_heads,
                                int num_kv_heads, int max_seq, int num_splits,
-                               float scale, int kv_fp8, hipStream_t stream);
+                               float scale, int kv_fp8, const PagedKV* paged,
+                               hipStream_t stream);
 
 // --- skinny_gemm.hip ---
 // Workgroup N-tile width (64 or 128) for M rows, and the split-K factor for

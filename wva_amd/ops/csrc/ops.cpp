@@ -4,8 +4,8 @@
 // The kernels' host entry points are declared in launch.h, which the .hip
 // files include too; nothing is re-declared here. Each kernel family has one
 // implementation below (decode attention, KV append, skinny linear, prefill
-// operands) behind its contiguous/paged or bf16/fp8 bindings, so a check or
-// a launch argument is edited in one place.
+// operands, ragged extend) behind its contiguous/paged or bf16/fp8 bindings,
+// so a check or a launch argument is edited in one place.
 
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
@@ -188,6 +188,53 @@ torch::Tensor rope_append_kv_paged(torch::Tensor qkv, torch::Tensor k_pages,
                                    double theta) {
   return rope_append_kv_impl(qkv, k_pages, v_pages, block_tables, positions,
                              num_q_heads, num_kv_heads, theta);
+}
+
+// Chunk append of ragged chunked prefill into a paged pool
+// (csrc/rope.hip rope_append_kv_chunk_kernel): row i < chunk_lens[b] of
+// sequence b is packed row q_starts[b] + i of qkv [T, (Hq+2Hk)*128] at
+// position prefix_lens[b] + i. Returns RoPE'd q [T, Hq, 128]; rows that no
+// sequence owns are unspecified. qkv may be a row range of a larger
+// row-contiguous tensor (the mixed iteration's GEMM output).
+torch::Tensor rope_append_kv_chunk_paged(
+    torch::Tensor qkv, torch::Tensor k_pages, torch::Tensor v_pages,
+    torch::Tensor block_tables, torch::Tensor prefix_lens,
+    torch::Tensor q_starts, torch::Tensor chunk_lens, int64_t max_chunk,
+    int64_t num_q_heads, int64_t num_kv_heads, double theta) {
+  check_bf16_contig(qkv, "qkv");
+  const bool kv_fp8 = check_kv_pair(k_pages, v_pages);
+  check_i32_contig(prefix_lens, "prefix_lens");
+  check_i32_contig(q_starts, "q_starts");
+  check_i32_contig(chunk_lens, "chunk_lens");
+  TORCH_CHECK(chunk_lens.dim() == 1 && chunk_lens.size(0) >= 1 &&
+                  chunk_lens.size(0) <= 65535,
+              "chunk_lens must be [B] with 1 <= B <= 65535");
+  const int64_t batch = chunk_lens.size(0);
+  TORCH_CHECK(prefix_lens.dim() == 1 && prefix_lens.size(0) == batch,
+              "prefix_lens must be [B] like chunk_lens");
+  TORCH_CHECK(q_starts.dim() == 1 && q_starts.size(0) == batch,
+              "q_starts must be [B] like chunk_lens");
+  const PagedKV paged = check_paged_pool(k_pages, block_tables, batch);
+  const int64_t max_seq = (int64_t)paged.max_blocks << paged.block_shift;
+  TORCH_CHECK(k_pages.size(1) == num_kv_heads, "Hk mismatch");
+  TORCH_CHECK(num_q_heads >= 1 && qkv.dim() == 2 &&
+                  qkv.size(1) == (num_q_heads + 2 * num_kv_heads) * 128,
+              "qkv must be [T, (Hq+2Hk)*128]");
+  TORCH_CHECK(qkv.size(0) >= 1 && qkv.size(0) < (1L << 31),
+              "need between 1 and 2^31 - 1 qkv rows");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0,
+              "qkv rows must be 16-byte aligned");
+  TORCH_CHECK(max_chunk >= 1 && max_chunk <= max_seq &&
+                  max_seq + max_chunk < (1L << 31),
+              "max_chunk must be in [1, max_blocks * block_size]");
+  auto q_out = torch::empty({qkv.size(0), num_q_heads, 128}, qkv.options());
+  launch_rope_append_kv_chunk(
+      qkv.data_ptr(), q_out.data_ptr(), k_pages.data_ptr(),
+      v_pages.data_ptr(), prefix_lens.data_ptr<int>(),
+      q_starts.data_ptr<int>(), chunk_lens.data_ptr<int>(), &paged,
+      (int)batch, (int)qkv.size(0), (int)max_chunk, (int)num_q_heads,
+      (int)num_kv_heads, (float)theta, kv_fp8 ? 1 : 0, current_stream());
+  return q_out;
 }
 
 torch::Tensor silu_mul_fused(torch::Tensor gate_up) {
@@ -383,7 +430,8 @@ int64_t skinny_linear_splits(int64_t M, int64_t N, int64_t K) {
 
 // Operand checks shared by prefill_attn, extend_attn and extend_attn_ragged:
 // q [T, Hq, 128] bf16 against head-major caches [>= batch, Hk, S_max, 128]
-// with G = Hq / Hk <= 8.
+// with G = Hq / Hk <= 8. With `paged` (already checked, check_paged_pool) the
+// caches are a pool and max_seq is max_blocks * block_size.
 struct PrefillOperands {
   bool kv_fp8;
   int num_q_heads, num_kv_heads, max_seq;
@@ -392,18 +440,24 @@ struct PrefillOperands {
 PrefillOperands check_prefill_operands(const torch::Tensor& q,
                                        const torch::Tensor& k_cache,
                                        const torch::Tensor& v_cache,
-                                       int64_t batch) {
+                                       int64_t batch,
+                                       const PagedKV* paged = nullptr) {
   check_bf16_contig(q, "q");
   const bool kv_fp8 = check_kv_pair(k_cache, v_cache);
   TORCH_CHECK(q.dim() == 3 && q.size(2) == 128, "q must be [T, Hq, 128]");
-  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(3) == 128,
-              "k_cache must be [B, Hk, S_max, 128]");
-  TORCH_CHECK(k_cache.size(0) >= batch, "cache holds fewer than B sequences");
+  if (!paged) {  // a pool's shape is check_paged_pool's
+    TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(3) == 128,
+                "k_cache must be [B, Hk, S_max, 128]");
+    TORCH_CHECK(k_cache.size(0) >= batch,
+                "cache holds fewer than B sequences");
+  }
   const int num_q_heads = q.size(1);
   const int num_kv_heads = k_cache.size(1);
   TORCH_CHECK(num_q_heads % num_kv_heads == 0, "Hq must divide by Hk");
   TORCH_CHECK(num_q_heads / num_kv_heads <= 8, "GQA group size must be <= 8");
-  return {kv_fp8, num_q_heads, num_kv_heads, (int)k_cache.size(2)};
+  return {kv_fp8, num_q_heads, num_kv_heads,
+          paged ? paged->max_blocks << paged->block_shift
+                : (int)k_cache.size(2)};
 }
 
 // Causal flash-attention prefill over the (already-populated) head-major
@@ -453,20 +507,27 @@ torch::Tensor extend_attn(torch::Tensor q, torch::Tensor k_cache,
 // three stay on the device (csrc/prefill_attention.hip, RAGGED). q/out:
 // [T, Hq, 128]; rows that no sequence owns read as 0. num_splits > 1 splits
 // the kv sweep over a workspace and merges (extend_attn_ragged_splits gives
-// the launch heuristic's count).
-torch::Tensor extend_attn_ragged(torch::Tensor q, torch::Tensor k_cache,
-                                 torch::Tensor v_cache,
-                                 torch::Tensor prefix_lens,
-                                 torch::Tensor q_starts,
-                                 torch::Tensor chunk_lens, int64_t max_chunk,
-                                 double scale, int64_t num_splits) {
+// the launch heuristic's count). With block_tables the caches are a paged
+// pool (check_paged_pool; csrc/prefill_attention.hip, PAGED) and the cache
+// size is max_blocks * block_size.
+torch::Tensor extend_attn_ragged_impl(
+    const torch::Tensor& q, const torch::Tensor& k_cache,
+    const torch::Tensor& v_cache,
+    const c10::optional<torch::Tensor>& block_tables,
+    const torch::Tensor& prefix_lens, const torch::Tensor& q_starts,
+    const torch::Tensor& chunk_lens, int64_t max_chunk, double scale,
+    int64_t num_splits) {
   check_i32_contig(prefix_lens, "prefix_lens");
   check_i32_contig(q_starts, "q_starts");
   check_i32_contig(chunk_lens, "chunk_lens");
   TORCH_CHECK(chunk_lens.dim() == 1 && chunk_lens.size(0) >= 1,
               "chunk_lens must be [B] with B >= 1");
   const int64_t batch = chunk_lens.size(0);
-  const PrefillOperands p = check_prefill_operands(q, k_cache, v_cache, batch);
+  PagedKV paged{};
+  if (block_tables.has_value())
+    paged = check_paged_pool(k_cache, *block_tables, batch);
+  const PrefillOperands p = check_prefill_operands(
+      q, k_cache, v_cache, batch, block_tables.has_value() ? &paged : nullptr);
   const int num_q_heads = p.num_q_heads;
   TORCH_CHECK(q.size(0) >= 1, "need at least one query row");
   TORCH_CHECK(prefix_lens.dim() == 1 && prefix_lens.size(0) == batch,
@@ -497,8 +558,30 @@ torch::Tensor extend_attn_ragged(torch::Tensor q, torch::Tensor k_cache,
       v_cache.data_ptr(), prefix_lens.data_ptr<int>(),
       q_starts.data_ptr<int>(), chunk_lens.data_ptr<int>(), (int)batch,
       (int)q.size(0), (int)max_chunk, num_q_heads, p.num_kv_heads, p.max_seq,
-      (int)num_splits, (float)scale, p.kv_fp8 ? 1 : 0, current_stream());
+      (int)num_splits, (float)scale, p.kv_fp8 ? 1 : 0,
+      block_tables.has_value() ? &paged : nullptr, current_stream());
   return out;
+}
+
+torch::Tensor extend_attn_ragged(torch::Tensor q, torch::Tensor k_cache,
+                                 torch::Tensor v_cache,
+                                 torch::Tensor prefix_lens,
+                                 torch::Tensor q_starts,
+                                 torch::Tensor chunk_lens, int64_t max_chunk,
+                                 double scale, int64_t num_splits) {
+  return extend_attn_ragged_impl(q, k_cache, v_cache, c10::nullopt,
+                                 prefix_lens, q_starts, chunk_lens, max_chunk,
+                                 scale, num_splits);
+}
+
+torch::Tensor extend_attn_ragged_paged(
+    torch::Tensor q, torch::Tensor k_pages, torch::Tensor v_pages,
+    torch::Tensor block_tables, torch::Tensor prefix_lens,
+    torch::Tensor q_starts, torch::Tensor chunk_lens, int64_t max_chunk,
+    double scale, int64_t num_splits) {
+  return extend_attn_ragged_impl(q, k_pages, v_pages, block_tables,
+                                 prefix_lens, q_starts, chunk_lens, max_chunk,
+                                 scale, num_splits);
 }
 
 int64_t extend_attn_ragged_splits(int64_t batch, int64_t num_q_heads,
@@ -683,6 +766,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("prefix_lens"), py::arg("q_starts"), py::arg("chunk_lens"),
         py::arg("max_chunk"), py::arg("scale"), py::arg("num_splits"));
+  m.def("extend_attn_ragged_paged", &extend_attn_ragged_paged,
+        "extend_attn_ragged over a paged KV pool [num_blocks, Hk, block_size, "
+        "128] through block tables [B, max_blocks]",
+        py::arg("q"), py::arg("k_pages"), py::arg("v_pages"),
+        py::arg("block_tables"), py::arg("prefix_lens"), py::arg("q_starts"),
+        py::arg("chunk_lens"), py::arg("max_chunk"), py::arg("scale"),
+        py::arg("num_splits"));
+  m.def("rope_append_kv_chunk_paged", &rope_append_kv_chunk_paged,
+        "RoPE on the packed qkv rows of ragged chunks + append of their K/V "
+        "rows into a paged KV pool; returns q [T, Hq, 128]",
+        py::arg("qkv"), py::arg("k_pages"), py::arg("v_pages"),
+        py::arg("block_tables"), py::arg("prefix_lens"), py::arg("q_starts"),
+        py::arg("chunk_lens"), py::arg("max_chunk"), py::arg("num_q_heads"),
+        py::arg("num_kv_heads"), py::arg("theta") = 500000.0);
   m.def("extend_attn_ragged_splits", &extend_attn_ragged_splits,
         "Split-KV factor extend_attn_ragged picks for these static shapes",
         py::arg("batch"), py::arg("num_q_heads"), py::arg("max_chunk"),

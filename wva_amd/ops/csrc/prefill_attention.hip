@@ -80,17 +80,8 @@ __device__ __forceinline__ float group16_sum(float v) {
 // no content of a device tensor takes a load or a store out of its buffer.
 #define WS_ROW (2 + HEAD_DIM)  // floats of one (row, head, split) partial
 
-// chunk_lens[b] clamped to [0, min(max_chunk, T)]
-__device__ __forceinline__ int ragged_len(const int* chunk_lens, int b,
-                                          int max_chunk, int total_rows) {
-  return min(max(chunk_lens[b], 0), min(max_chunk, total_rows));
-}
-
-// q_starts[b] clamped to [0, T - len_b]
-__device__ __forceinline__ int ragged_start(const int* q_starts, int b,
-                                            int len_b, int total_rows) {
-  return min(max(q_starts[b], 0), total_rows - len_b);
-}
+// ragged_len / ragged_start (the clamps of chunk_lens and q_starts) are in
+// common.h; the chunk append of rope.hip applies the same ones.
 
 // first float of the partial of row r (0..63) of q-tile `tile` of (b, h)
 // = bh, split `split` of `num_splits`; `tiles` = ceil(max_chunk / 64)
@@ -100,7 +91,63 @@ __device__ __forceinline__ long ragged_ws_off(int bh, int tiles, int tile,
   return ((((long)bh * tiles + tile) * QT + r) * num_splits + split) * WS_ROW;
 }
 
-template <bool KV_FP8, bool HAS_PREFIX, bool RAGGED = false>
+// PAGED (implies RAGGED): k_cache / v_cache are pools [num_blocks, Hk,
+// block_size, 128] with block_size = 1 << block_shift in {16, 32, 64} and
+// sequence b's positions i·block_size .. are the page block_tables[b, i];
+// max_seq is max_blocks · block_size. Only addresses change: the tiles, the
+// mask, the softmax and the stores are those of RAGGED, so on the same rows
+// and split count the output has the bits of RAGGED on the gathered cache.
+//
+// Addressing rules (those of the paged decode kernels, attention.hip), which
+// keep every load inside the pool whatever the tables hold:
+//   * the live rows end at kv_len = min(P_b + len_b, max_blocks·block_size);
+//   * a position at or past kv_len is clamped to kv_len − 1 BEFORE the table
+//     lookup, so entries at index >= ceil(kv_len / block_size) are never
+//     dereferenced;
+//   * an id read from the table is clamped into [0, num_blocks − 1] before it
+//     forms an address, and page offsets are formed in 64-bit.
+// A corrupt table gives wrong numbers, never a load outside the pool.
+//
+// Every aligned group of 16 positions lies inside one page, so a wave's score
+// n-tile has one page and a 64-position kv tile has four. PrefillTilePages
+// holds, per group, the first row of this kv-head's run in that page (in pool
+// rows, 64-bit). The four ids are fetched once per tile through wave-uniform
+// indices (scalar loads), and the loop asks for the NEXT tile's ids
+// (kt0 + kt_step: the split interleaving) before it stages the current
+// tile, so the dependent id load at the head of a tile is a tile old when
+// its addresses are formed and never waits in front of the PV phase.
+struct PrefillTilePages {
+  long row0[4];
+
+  // rows of group `g`; a select chain keeps row0[] in registers where a
+  // runtime index would go to scratch. The V staging passes a wave-uniform g
+  // (a wave stages one position per pass: idx >> 6 with 64 lanes), read
+  // through readfirstlane so that the chain runs on the scalar unit.
+  __device__ __forceinline__ long pick(int g) const {
+    return g == 0 ? row0[0] : g == 1 ? row0[1] : g == 2 ? row0[2] : row0[3];
+  }
+};
+
+// `table_row` = block_tables + b·max_blocks, kv_len >= 1. Group g covers the
+// positions kt0 + 16g .. kt0 + 16g + 15; one that starts at or past kv_len
+// takes the page of position kv_len − 1, where its clamped rows read. kt0 may
+// be a tile past the sweep (the prefetch of a last iteration): it is clamped
+// like any position, so nothing new is dereferenced.
+__device__ __forceinline__ PrefillTilePages prefill_tile_pages(
+    const int* __restrict__ table_row, int kt0, int kv_len, int kvh,
+    int num_kv_heads, int block_shift, int num_blocks) {
+  PrefillTilePages pages;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const int pos = min(max(kt0 + 16 * g, 0), kv_len - 1);
+    const int id = min(max(table_row[pos >> block_shift], 0), num_blocks - 1);
+    pages.row0[g] = ((long)id * num_kv_heads + kvh) << block_shift;
+  }
+  return pages;
+}
+
+template <bool KV_FP8, bool HAS_PREFIX, bool RAGGED = false,
+          bool PAGED = false>
 __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
     bf16* __restrict__ out,            // [T, Hq, 128]
     const bf16* __restrict__ q,        // [T, Hq, 128]
@@ -116,8 +163,14 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
     const int* __restrict__ q_starts,    // [B], RAGGED only
     const int* __restrict__ chunk_lens,  // [B], RAGGED only
     float* __restrict__ ws,              // partials, RAGGED with splits > 1
-    const int total_rows) {              // T, RAGGED only
+    const int total_rows,                // T, RAGGED only
+    // PAGED only (null / 0 otherwise); max_seq = max_blocks << block_shift
+    const int* __restrict__ block_tables,  // [B, max_blocks]
+    const int max_blocks,
+    const int block_shift,               // log2(block_size)
+    const int num_blocks) {
   static_assert(HAS_PREFIX || !RAGGED, "RAGGED implies HAS_PREFIX");
+  static_assert(RAGGED || !PAGED, "PAGED implies RAGGED");
   const int bh = blockIdx.x;           // b * Hq + h
   const int b = bh / num_q_heads;
   const int h = bh % num_q_heads;
@@ -161,7 +214,9 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
   __shared__ unsigned short v_smem_t[HEAD_DIM * VT_ROW];
   __shared__ float p_smem[NUM_WAVES][16][P_ROW];
 
-  const long slab_off = ((long)b * num_kv_heads + kvh) * max_seq * HEAD_DIM;
+  // PAGED: the pool itself; the kv-head is part of a page's rows
+  const long slab_off =
+      PAGED ? 0 : ((long)b * num_kv_heads + kvh) * max_seq * HEAD_DIM;
   const bf16* k_slab = reinterpret_cast<const bf16*>(k_cache) + slab_off;
   const fp8_t* k_slab8 = reinterpret_cast<const fp8_t*>(k_cache) + slab_off;
   const unsigned int* v_base = reinterpret_cast<const unsigned int*>(
@@ -209,8 +264,25 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
   // causal upper bound of this q-tile's sweep
   const int kv_end = min(q_pos0 + qt0 + QT, kv_len);
 
+  // PAGED: the pages of the tile at hand, and those of the tile after it,
+  // which are asked for a whole tile before they form an address
+  [[maybe_unused]] const int* table_row = nullptr;
+  [[maybe_unused]] PrefillTilePages pages, next_pages;
+  [[maybe_unused]] const int block_mask = (1 << block_shift) - 1;
+  if constexpr (PAGED) {
+    table_row = block_tables + (long)b * max_blocks;
+    next_pages = prefill_tile_pages(table_row, kt_first, kv_len, kvh,
+                                    num_kv_heads, block_shift, num_blocks);
+  }
+
   for (int kt0 = kt_first; kt0 < kv_end; kt0 += kt_step) {
     const int kn = min(KT_POS, kv_len - kt0);
+    if constexpr (PAGED) {
+      pages = next_pages;
+      next_pages =
+          prefill_tile_pages(table_row, kt0 + kt_step, kv_len, kvh,
+                             num_kv_heads, block_shift, num_blocks);
+    }
 
     // --- stage V tile transposed (cooperative, all waves): each
     // thread reads one dim-pair at one position (coalesced along the
@@ -223,8 +295,14 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
            idx += NUM_WAVES * WAVE_SIZE) {
         const int pos = idx >> 6;          // 64 pairs per position row
         const int d2 = idx & 63;
-        const unsigned short packed = *reinterpret_cast<const unsigned short*>(
-            v_src + (long)pos * HEAD_DIM + 2 * d2);
+        const fp8_t* v_row = v_src + (long)pos * HEAD_DIM;
+        if constexpr (PAGED) {  // rows 0..kn-1 are live: no clamp
+          const int upos = __builtin_amdgcn_readfirstlane(pos);
+          v_row = v_base8 +
+                  (pages.pick(upos >> 4) + (upos & block_mask)) * HEAD_DIM;
+        }
+        const unsigned short packed =
+            *reinterpret_cast<const unsigned short*>(v_row + 2 * d2);
         const float2_vt f = unpk2_fp8(packed);
         const bf16 b0 = f2bf(f[0]);
         const bf16 b1 = f2bf(f[1]);
@@ -240,7 +318,14 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
            idx += NUM_WAVES * WAVE_SIZE) {
         const int pos = idx >> 6;          // 64 dwords per position row
         const int d2 = idx & 63;           // dim pair
-        const unsigned int val = v_src[idx];
+        unsigned int val;
+        if constexpr (PAGED) {  // rows 0..kn-1 are live: no clamp
+          const int upos = __builtin_amdgcn_readfirstlane(pos);
+          val = v_base[(pages.pick(upos >> 4) + (upos & block_mask)) *
+                           (HEAD_DIM / 2) + d2];
+        } else {
+          val = v_src[idx];
+        }
         v_smem_t[(2 * d2) * VT_ROW + pos] = (unsigned short)(val & 0xffffu);
         v_smem_t[(2 * d2 + 1) * VT_ROW + pos] =
             (unsigned short)(val >> 16);
@@ -256,14 +341,18 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) {
         const int kpos = kt0 + 16 * nt + (lane % 16);
-        const int kpos_c = kpos < max_seq ? kpos : max_seq - 1;
+        // row of the slab, or of the pool (PAGED: clamped to the live rows
+        // before the page is chosen, see PrefillTilePages)
+        long kpos_c = kpos < max_seq ? kpos : max_seq - 1;
+        if constexpr (PAGED)
+          kpos_c = pages.row0[nt] + (min(kpos, kv_len - 1) & block_mask);
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
           bf16x8_frag k_frag;
           if constexpr (KV_FP8) {
             const unsigned short* src =
                 reinterpret_cast<const unsigned short*>(
-                    k_slab8 + (long)kpos_c * HEAD_DIM + 32 * kk + col0);
+                    k_slab8 + kpos_c * HEAD_DIM + 32 * kk + col0);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               const float2_vt f = unpk2_fp8(src[j]);
@@ -272,7 +361,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
             }
           } else {
             const short* krow = reinterpret_cast<const short*>(
-                k_slab + (long)kpos_c * HEAD_DIM);
+                k_slab + kpos_c * HEAD_DIM);
             k_frag =
                 *reinterpret_cast<const bf16x8_frag*>(krow + 32 * kk + col0);
           }
@@ -418,6 +507,22 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(
   }
 }
 
+// The two PAGED instantiations are new kernels and are instantiated here
+// without the packed fp32 forms (common.h NO_PACKED_FP32 gives the reason).
+// The source of their arithmetic is the contiguous instantiations'; scalar
+// and packed fp32 ops round alike, so the bits are too (the GPU tests hold
+// that), and the same attribute on the contiguous RAGGED kernels changed no
+// timing (profiles/paged_extend_packed_ab.json).
+#define PREFILL_PAGED_INSTANCE(KV_FP8)                                        \
+  template __global__ NO_PACKED_FP32 void                                     \
+  prefill_attn_kernel<KV_FP8, true, true, true>(                              \
+      bf16*, const bf16*, const void*, const void*, const int*, int, int,     \
+      int, int, int, float, const int*, const int*, float*, int, const int*,  \
+      int, int, int)
+PREFILL_PAGED_INSTANCE(false);
+PREFILL_PAGED_INSTANCE(true);
+#undef PREFILL_PAGED_INSTANCE
+
 // Merge of the split sweep: out row = sum_s exp(m_s - m) o_s / sum_s
 // exp(m_s - m) s_s with m = max_s m_s. Grid (B·Hq, ceil(max_chunk/64), 16):
 // a wave per row (4 rows per workgroup), a lane per dim pair; the m_s are
@@ -481,13 +586,13 @@ static void launch_prefill_kernel(
                        0, stream, (bf16*)out, (const bf16*)q, k_cache,
                        v_cache, prefix_lens, batch, rows, num_q_heads,
                        num_kv_heads, max_seq, scale, nullptr, nullptr,
-                       nullptr, 0);
+                       nullptr, 0, nullptr, 0, 0, 0);
   } else {
     hipLaunchKernelGGL((prefill_attn_kernel<false, HAS_PREFIX>), grid, block,
                        0, stream, (bf16*)out, (const bf16*)q, k_cache,
                        v_cache, prefix_lens, batch, rows, num_q_heads,
                        num_kv_heads, max_seq, scale, nullptr, nullptr,
-                       nullptr, 0);
+                       nullptr, 0, nullptr, 0, 0, 0);
   }
 }
 
@@ -536,14 +641,21 @@ extern "C" void launch_extend_attn_ragged(
     const void* v_cache, const int* prefix_lens, const int* q_starts,
     const int* chunk_lens, int batch, int total_rows, int max_chunk,
     int num_q_heads, int num_kv_heads, int max_seq, int num_splits,
-    float scale, int kv_fp8, hipStream_t stream) {
-  const auto kernel = kv_fp8 ? prefill_attn_kernel<true, true, true>
-                             : prefill_attn_kernel<false, true, true>;
+    float scale, int kv_fp8, const PagedKV* paged, hipStream_t stream) {
+  const auto kernel =
+      paged ? (kv_fp8 ? prefill_attn_kernel<true, true, true, true>
+                      : prefill_attn_kernel<false, true, true, true>)
+            : (kv_fp8 ? prefill_attn_kernel<true, true, true>
+                      : prefill_attn_kernel<false, true, true>);
+  const PagedKV p = paged ? *paged : PagedKV{nullptr, 0, 0, 0};
+  if (paged) max_seq = p.max_blocks << p.block_shift;
   const dim3 grid(batch * num_q_heads, (max_chunk + QT - 1) / QT, num_splits);
   hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, (bf16*)out,
                      (const bf16*)q, k_cache, v_cache, prefix_lens, batch,
                      max_chunk, num_q_heads, num_kv_heads, max_seq, scale,
-                     q_starts, chunk_lens, (float*)ws, total_rows);
+                     q_starts, chunk_lens, (float*)ws, total_rows,
+                     p.block_tables, p.max_blocks, p.block_shift,
+                     p.num_blocks);
   if (num_splits > 1) {
     hipLaunchKernelGGL(extend_ragged_merge_kernel,
                        dim3(grid.x, grid.y, QT / MERGE_ROWS),

@@ -1,7 +1,7 @@
 // Fused rotary position embedding (NeoX/Llama style, non-interleaved
 // half-rotation) — MI355X (gfx950).
 //
-// Two entry points:
+// Three entry points:
 //  * rope_kernel: in-place RoPE on contiguous q [T,Hq,D] / k [T,Hk,D]
 //    (kept for tests and generic use).
 //  * rope_append_kv_kernel: the decode fast path. Reads the UN-SLICED
@@ -14,7 +14,12 @@
 //    instantiations append into a paged pool [num_blocks, Hk, block_size,
 //    D] through block tables; the rotation code is the same.
 //
-// Grid: one workgroup per token; 256 threads cover heads × D/2 pairs.
+//  * rope_append_kv_chunk_kernel: the chunked-prefill append into a paged
+//    pool, several rows per workgroup with 16-byte accesses (see its own
+//    comment).
+//
+// Grid of the first two: one workgroup per token; 256 threads cover heads ×
+// D/2 pairs.
 
 #include "common.h"
 #include "launch.h"
@@ -255,6 +260,213 @@ __global__ void rope_append_kv_fp8_kernel(
         reinterpret_cast<unsigned short*>(v_cache + row0 + kh * head_stride);
     if (has_row) dst[d2] = pk2_fp8(bf2f(v2.x), bf2f(v2.y));
   }
+}
+
+// ---------------------------------------------------------------------------
+// Chunk append (ragged chunked prefill over a paged pool): one launch turns
+// the packed qkv rows of all in-flight chunks into RoPE'd q_out and into
+// rotated K / raw V rows of the pool. The decode append above is a workgroup
+// per token with 2-byte accesses; here hundreds of rows come per launch.
+//
+// Grid (row block, sequence), CHUNK_ROWS rows per workgroup, a WAVE PER ROW.
+// Row i < len_b of sequence b is packed row q_starts[b] + i at position
+// P_b + i: arithmetic, no search and no per-row index tensor. len_b and
+// q_starts[b] take the clamps of the attention kernel (common.h), P_b its
+// clamp to [0, max_blocks · block_size]; workgroups past len_b return.
+//
+// Per row (head_dim = 128, 64 rotation pairs):
+//   * lane d computes cos/sin of (position, d) ONCE and leaves them in the
+//     wave's LDS pane; every head of the row reuses them (the decode append
+//     recomputes __powf + __sincosf per head pair);
+//   * the row's page is looked up once (paged_row_offset, wave-uniform);
+//   * lane (slot = lane / 8, j = lane % 8) then owns dims 8j .. 8j+7 and
+//     64+8j .. 64+8j+7 of heads slot, slot + 8, ...: two 16-byte loads give
+//     the 8 pairs, which it rotates with its 8 (cos, sin) held in registers
+//     and writes with two 16-byte stores (bf16) or two 8-byte stores (the
+//     same 8 elements as e4m3). V rows move the same way without rotation.
+//     Eight lanes cover one 128-byte half row, so every access of a wave is
+//     whole 128-byte lines.
+// The angle is rope_cos_sin's (float64, reduced to turns) for both cache
+// dtypes: formed once per (row, d) it costs 64 double evaluations a row,
+// where the decode append would pay it per head, and it keeps q and a bf16 K
+// within one bf16 rounding of the exact rotation at every position up to
+// 131071 (rotate_pair's float32 angle is off by up to 2^-8 rad there).
+// A row without a page skips its K/V stores and still writes q_out.
+// ---------------------------------------------------------------------------
+#define CHUNK_ROWS 4     // rows (= waves) per workgroup
+#define CHUNK_D 128      // head_dim of the chunked-prefill path
+#define CHUNK_HALF (CHUNK_D / 2)
+
+// 8 bf16 (raw bits) as one 16-byte access; `p` is 16-byte aligned
+__device__ __forceinline__ bf16x8_frag load_bf16x8(const bf16* p) {
+  return *reinterpret_cast<const bf16x8_frag*>(p);
+}
+
+__device__ __forceinline__ void store_bf16x8(bf16* p, bf16x8_frag x) {
+  *reinterpret_cast<bf16x8_frag*>(p) = x;
+}
+
+__device__ __forceinline__ float bf_bits2f(short bits) {
+  return __uint_as_float((unsigned int)(unsigned short)bits << 16);
+}
+
+// 8 floats -> 8 adjacent e4m3 bytes, one 8-byte store
+__device__ __forceinline__ void store_fp8x8(fp8_t* p, const float (&f)[8]) {
+  unsigned int w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0u, false);
+  w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w0, true);
+  unsigned int w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], 0u, false);
+  w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], w1, true);
+  *reinterpret_cast<uint2*>(p) = uint2{w0, w1};
+}
+
+// One half row (8 elements at `dst`) of a pool row: bf16 as is, or as e4m3.
+template <bool KV_FP8>
+__device__ __forceinline__ void store_kv_x8(void* cache, long elem,
+                                            const float (&f)[8]) {
+  if constexpr (KV_FP8) {
+    store_fp8x8(reinterpret_cast<fp8_t*>(cache) + elem, f);
+  } else {
+    bf16x8_frag o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = f2bf_bits(f[e]);
+    store_bf16x8(reinterpret_cast<bf16*>(cache) + elem, o);
+  }
+}
+
+template <bool KV_FP8>
+__global__ NO_PACKED_FP32 __launch_bounds__(WAVE_SIZE* CHUNK_ROWS) void
+rope_append_kv_chunk_kernel(
+    const bf16* __restrict__ qkv,   // [T, (Hq + 2·Hk) · 128], packed rows
+    bf16* __restrict__ q_out,       // [T, Hq, 128]
+    void* __restrict__ k_cache,     // [num_blocks, Hk, block_size, 128]
+    void* __restrict__ v_cache,     // bf16 | e4m3
+    const int* __restrict__ prefix_lens,  // [B]
+    const int* __restrict__ q_starts,     // [B]
+    const int* __restrict__ chunk_lens,   // [B]
+    const int max_chunk,
+    const int total_rows,           // T
+    const int num_q_heads,
+    const int num_kv_heads,
+    const double log2_theta,
+    const int* __restrict__ block_tables,  // [B, max_blocks]
+    const int max_blocks,
+    const int block_shift,          // log2(block_size)
+    const int num_blocks) {
+  const int b = blockIdx.y;
+  const int len_b = ragged_len(chunk_lens, b, max_chunk, total_rows);
+  if ((int)blockIdx.x * CHUNK_ROWS >= len_b) return;  // whole workgroup
+  const int row_start = ragged_start(q_starts, b, len_b, total_rows);
+  const int max_seq = max_blocks << block_shift;
+  const int prefix = min(max(prefix_lens[b], 0), max_seq);
+  const int lane = threadIdx.x & (WAVE_SIZE - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE_SIZE);
+  const int i = blockIdx.x * CHUNK_ROWS + wave;  // row of the chunk
+  const int pos = prefix + i;
+
+  // cos/sin of (pos, d = lane), once per row
+  __shared__ __align__(16) float cos_smem[CHUNK_ROWS][CHUNK_HALF];
+  __shared__ __align__(16) float sin_smem[CHUNK_ROWS][CHUNK_HALF];
+  {
+    const RopeCosSin cs = rope_cos_sin(lane, CHUNK_D, pos, log2_theta);
+    cos_smem[wave][lane] = cs.c;
+    sin_smem[wave][lane] = cs.s;
+  }
+  __syncthreads();
+  if (i >= len_b) return;  // the waves of a partial last block
+
+  const int j = lane & 7;      // dims 8j..8j+7 of each half
+  const int slot = lane >> 3;  // heads slot, slot + 8, ...
+  float c[8], s[8];
+#pragma unroll
+  for (int e = 0; e < 8; e += 4) {
+    const float4 c4 =
+        *reinterpret_cast<const float4*>(&cos_smem[wave][8 * j + e]);
+    const float4 s4 =
+        *reinterpret_cast<const float4*>(&sin_smem[wave][8 * j + e]);
+    c[e] = c4.x, c[e + 1] = c4.y, c[e + 2] = c4.z, c[e + 3] = c4.w;
+    s[e] = s4.x, s[e + 1] = s4.y, s[e + 2] = s4.z, s[e + 3] = s4.w;
+  }
+
+  const long row = row_start + i;  // packed row
+  const bf16* src =
+      qkv + row * (num_q_heads + 2 * num_kv_heads) * CHUNK_D + 8 * j;
+  bf16* q_dst = q_out + row * num_q_heads * CHUNK_D + 8 * j;
+  // element offset of kv-head 0's pool row (-1: no page) and the kv-head
+  // stride, once per row
+  const long kv_row0 =
+      paged_row_offset(block_tables, b, pos, max_blocks, block_shift,
+                       num_blocks, num_kv_heads, CHUNK_D);
+  const long head_stride = (long)CHUNK_D << block_shift;
+  const bool has_row = kv_row0 >= 0;
+
+  // q heads, then k heads: rotate
+  for (int head = slot; head < num_q_heads + num_kv_heads; head += 8) {
+    const bf16x8_frag lo = load_bf16x8(src + (long)head * CHUNK_D);
+    const bf16x8_frag hi =
+        load_bf16x8(src + (long)head * CHUNK_D + CHUNK_HALF);
+    float r1[8], r2[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float x1 = bf_bits2f(lo[e]);
+      const float x2 = bf_bits2f(hi[e]);
+      r1[e] = x1 * c[e] - x2 * s[e];
+      r2[e] = x2 * c[e] + x1 * s[e];
+    }
+    if (head < num_q_heads) {
+      bf16x8_frag o1, o2;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        o1[e] = f2bf_bits(r1[e]);
+        o2[e] = f2bf_bits(r2[e]);
+      }
+      store_bf16x8(q_dst + (long)head * CHUNK_D, o1);
+      store_bf16x8(q_dst + (long)head * CHUNK_D + CHUNK_HALF, o2);
+    } else if (has_row) {
+      const long elem = kv_row0 + (head - num_q_heads) * head_stride + 8 * j;
+      store_kv_x8<KV_FP8>(k_cache, elem, r1);
+      store_kv_x8<KV_FP8>(k_cache, elem + CHUNK_HALF, r2);
+    }
+  }
+  if (!has_row) return;
+  // v heads: copy (bf16 bits as they are, or the e4m3 cast)
+  const bf16* vsrc = src + (long)(num_q_heads + num_kv_heads) * CHUNK_D;
+  for (int kh = slot; kh < num_kv_heads; kh += 8) {
+    const bf16x8_frag lo = load_bf16x8(vsrc + (long)kh * CHUNK_D);
+    const bf16x8_frag hi =
+        load_bf16x8(vsrc + (long)kh * CHUNK_D + CHUNK_HALF);
+    const long elem = kv_row0 + kh * head_stride + 8 * j;
+    if constexpr (KV_FP8) {
+      float f1[8], f2[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        f1[e] = bf_bits2f(lo[e]);
+        f2[e] = bf_bits2f(hi[e]);
+      }
+      store_kv_x8<true>(v_cache, elem, f1);
+      store_kv_x8<true>(v_cache, elem + CHUNK_HALF, f2);
+    } else {
+      bf16* dst = reinterpret_cast<bf16*>(v_cache) + elem;
+      store_bf16x8(dst, lo);
+      store_bf16x8(dst + CHUNK_HALF, hi);
+    }
+  }
+}
+
+extern "C" void launch_rope_append_kv_chunk(
+    const void* qkv, void* q_out, void* k_cache, void* v_cache,
+    const int* prefix_lens, const int* q_starts, const int* chunk_lens,
+    const PagedKV* paged, int batch, int total_rows, int max_chunk,
+    int num_q_heads, int num_kv_heads, float theta, int kv_fp8,
+    hipStream_t stream) {
+  const auto kernel = kv_fp8 ? rope_append_kv_chunk_kernel<true>
+                             : rope_append_kv_chunk_kernel<false>;
+  const dim3 grid((max_chunk + CHUNK_ROWS - 1) / CHUNK_ROWS, batch);
+  hipLaunchKernelGGL(kernel, grid, dim3(WAVE_SIZE * CHUNK_ROWS), 0, stream,
+                     (const bf16*)qkv, (bf16*)q_out, k_cache, v_cache,
+                     prefix_lens, q_starts, chunk_lens, max_chunk, total_rows,
+                     num_q_heads, num_kv_heads, log2((double)theta),
+                     paged->block_tables, paged->max_blocks,
+                     paged->block_shift, paged->num_blocks);
 }
 
 extern "C" void launch_rope(
