@@ -555,18 +555,41 @@ def moe_route(router_logits: torch.Tensor, top_k: int):
     return moe_route_ref(router_logits, top_k)
 
 
+MOE_VARIANTS = (None, "stream", "tiled")
+
+
+def _check_moe_variant(variant):
+    if variant not in MOE_VARIANTS:
+        raise ValueError(
+            f"variant must be one of {MOE_VARIANTS}, got {variant!r}"
+        )
+
+
+def moe_variant(tokens: int, top_k: int, num_experts: int) -> str:
+    """Kernel family the MoE GEMMs take for these static shapes when no
+    variant is forced: "stream" (64-row m-tiles, weights streamed per
+    wave; decode) or "tiled" (128-row m-tiles staged through LDS;
+    prefill). Never "tiled" below 128 routed rows per expert."""
+    tiled = _require_ext().moe_rule_tiled(tokens, top_k, num_experts)
+    return "tiled" if tiled else "stream"
+
+
 def moe_gate_up_swiglu(
     x: torch.Tensor,
     w_gate_up: torch.Tensor,
     expert_offsets: torch.Tensor,
     sorted_slots: torch.Tensor,
     top_k: int,
+    variant: Optional[str] = None,
 ) -> torch.Tensor:
     """Grouped gate_up GEMM + SwiGLU over the routed rows only: bf16
-    [T*K, I] in expert-sorted order, against the stacked [E, 2I, H]."""
+    [T*K, I] in expert-sorted order, against the stacked [E, 2I, H].
+    `variant` forces a kernel family (see moe_variant, which None
+    follows); the CPU reference has none and ignores it."""
+    _check_moe_variant(variant)
     if x.is_cuda:
         return _require_ext().moe_gate_up_swiglu(
-            x, w_gate_up, expert_offsets, sorted_slots, top_k
+            x, w_gate_up, expert_offsets, sorted_slots, top_k, variant
         )
     return moe_gate_up_swiglu_ref(
         x, w_gate_up, expert_offsets, sorted_slots, top_k
@@ -579,12 +602,15 @@ def moe_down_combine(
     topk_w: torch.Tensor,
     expert_offsets: torch.Tensor,
     sorted_slots: torch.Tensor,
+    variant: Optional[str] = None,
 ) -> torch.Tensor:
     """Grouped down GEMM against the stacked [E, H, I] + top-k combine:
-    bf16 [T, H], summed in a fixed order (deterministic)."""
+    bf16 [T, H], summed in a fixed order (deterministic). `variant` as in
+    moe_gate_up_swiglu."""
+    _check_moe_variant(variant)
     if act_sorted.is_cuda:
         return _require_ext().moe_down_combine(
-            act_sorted, w_down, topk_w, expert_offsets, sorted_slots
+            act_sorted, w_down, topk_w, expert_offsets, sorted_slots, variant
         )
     return moe_down_combine_ref(
         act_sorted, w_down, topk_w, expert_offsets, sorted_slots
@@ -594,7 +620,8 @@ def moe_down_combine(
 def moe_down_num_splits(
     tokens: int, top_k: int, num_experts: int, hidden: int, inter: int
 ) -> int:
-    """Split-K factor the down GEMM kernel picks for these static shapes."""
+    """Split-K factor the streaming down GEMM kernel picks for these
+    static shapes (the tiled kernel does not split K)."""
     return int(
         _require_ext().moe_down_splits(
             tokens, top_k, num_experts, hidden, inter
@@ -608,16 +635,21 @@ def moe_mlp(
     w_gate_up: torch.Tensor,
     w_down: torch.Tensor,
     top_k: int,
+    variant: Optional[str] = None,
 ) -> torch.Tensor:
     """Routed expert MLP: x [T, H] bf16, router_logits [T, E] fp32,
     stacked expert weights [E, 2I, H] / [E, H, I] → bf16 [T, H].
 
     Only routed experts' weights are streamed and only routed tokens are
-    multiplied; no step syncs with the host (csrc/moe.hip)."""
+    multiplied; no step syncs with the host (csrc/moe.hip). `variant`
+    goes to both GEMMs; None follows moe_variant in each of them."""
+    _check_moe_variant(variant)
     if x.is_cuda:
         _, topk_w, offsets, slots = moe_route(router_logits, top_k)
-        act = moe_gate_up_swiglu(x, w_gate_up, offsets, slots, top_k)
-        return moe_down_combine(act, w_down, topk_w, offsets, slots)
+        act = moe_gate_up_swiglu(x, w_gate_up, offsets, slots, top_k, variant)
+        return moe_down_combine(
+            act, w_down, topk_w, offsets, slots, variant
+        )
     return moe_mlp_ref(x, router_logits, w_gate_up, w_down, top_k).to(x.dtype)
 
 

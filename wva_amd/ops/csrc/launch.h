@@ -135,24 +135,33 @@ void launch_skinny_gemm(void* c, void* ws, const void* a, const void* w,
 int moe_num_m_tiles(int TK, int E);
 int moe_down_nsub(int TK);
 int moe_down_num_splits(int TK, int E, int H, int I);
+// The two GEMMs come in two families: streaming (64-row m-tiles, no LDS,
+// split-K down; the three helpers above describe it) and tiled (128-row
+// m-tiles staged through LDS, no split-K). moe_use_tiled is the static-shape
+// rule a call with no forced variant follows (1 = tiled);
+// moe_num_m_tiles_tiled the m-tile bound of the tiled grid.
+int moe_use_tiled(int TK, int E);
+int moe_num_m_tiles_tiled(int TK, int E);
 // logits float [T, E] → topk_idx [T, K], topk_w float [T, K],
 // expert_offsets [E+1], sorted_slots [T·K].
 void launch_moe_route(int* topk_idx, float* topk_w, int* expert_offsets,
                       int* sorted_slots, const float* logits, int T, int E,
                       int K, hipStream_t stream);
 // act [T·top_k, I] = silu(g)·u of x [T, H] · w [E, 2I, H]^T, rows in
-// expert-sorted order.
+// expert-sorted order. `tiled` picks the kernel family.
 void launch_moe_gate_up_swiglu(void* act, const void* x, const void* w,
                                const int* expert_offsets,
                                const int* sorted_slots, int T, int E,
-                               int top_k, int H, int I, hipStream_t stream);
+                               int top_k, int H, int I, int tiled,
+                               hipStream_t stream);
 // out [T, H] = Σ_k topk_w · (act · w [E, H, I]^T); `ws` holds
-// num_splits·T·top_k·H floats and is always used.
+// num_splits·T·top_k·H floats and is always used. With `tiled` num_splits
+// must be 1: the tiled kernel does not split K, ws is T·top_k·H floats.
 void launch_moe_down_combine(void* out, float* ws, const void* act,
                              const void* w, const float* topk_w,
                              const int* expert_offsets,
                              const int* sorted_slots, int T, int E, int top_k,
-                             int H, int I, int num_splits,
+                             int H, int I, int num_splits, int tiled,
                              hipStream_t stream);
 
 }  // extern "C"

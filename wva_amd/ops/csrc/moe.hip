@@ -1,4 +1,4 @@
-// Device-side routed MoE expert MLP for decode — MI355X (gfx950).
+// Device-side routed MoE expert MLP, decode and prefill — MI355X (gfx950).
 //
 //   route:    fp32 router logits [T,E] → top-k ids/weights, per-expert
 //             offsets and the stable expert-sorted slot list
@@ -21,6 +21,14 @@
 // (expert, m-tile) by scanning expert_offsets. Workgroups past the last
 // non-empty tile exit before touching a weight, so an expert with no
 // routed rows streams nothing.
+//
+// That streaming family is the decode shape: a handful of rows per expert.
+// Once an expert owns 128 rows and more (prefill) every 64-row m-tile would
+// stream the expert again, so a second, compute-shaped family follows it:
+// moe_gate_up_swiglu_tiled_kernel and moe_down_tiled_kernel stage 128-row A
+// and W tiles through LDS and share them among the four waves (see "tiled
+// grouped GEMMs" below). moe_use_tiled picks the family from (T·K, E) alone;
+// route, sort and combine are common to both.
 //
 // Fragment convention as in skinny_gemm.hip: identical lane→k bijection
 // for A and B (a different one than skinny_gemm's, see moe_mma_stream);
@@ -134,11 +142,13 @@ __global__ __launch_bounds__(256) void moe_sort_kernel(
 struct MoeTile {
   int expert;
   int row0;  // first sorted position of this m-tile
-  int rows;  // live rows, 1..MOE_BM
+  int rows;  // live rows, 1..BM
 };
 
-// Map a linear m-tile index onto (expert, m-tile within expert). Uniform
-// across the workgroup (scalar loads); false = past the last live tile.
+// Map a linear m-tile index onto (expert, m-tile within expert) for m-tiles
+// of BM sorted rows. Uniform across the workgroup (scalar loads); false =
+// past the last live tile.
+template <int BM>
 __device__ __forceinline__ bool moe_find_tile(
     const int* __restrict__ expert_offsets, const int E, int tile,
     MoeTile& out) {
@@ -146,11 +156,11 @@ __device__ __forceinline__ bool moe_find_tile(
   for (int e = 0; e < E; ++e) {
     const int end = expert_offsets[e + 1];
     const int n_e = end - begin;
-    const int tiles_e = (n_e + MOE_BM - 1) / MOE_BM;
+    const int tiles_e = (n_e + BM - 1) / BM;
     if (tile < tiles_e && begin >= 0) {
       out.expert = e;
-      out.row0 = begin + tile * MOE_BM;
-      out.rows = min(MOE_BM, n_e - tile * MOE_BM);
+      out.row0 = begin + tile * BM;
+      out.rows = min(BM, n_e - tile * BM);
       return true;
     }
     tile -= tiles_e;
@@ -228,7 +238,7 @@ __global__ __launch_bounds__(256, 2) void moe_gate_up_swiglu_kernel(
     const int* __restrict__ sorted_slots,
     const int T, const int E, const int top_k, const int H, const int I) {
   MoeTile tile;
-  if (!moe_find_tile(expert_offsets, E, blockIdx.y, tile)) return;
+  if (!moe_find_tile<MOE_BM>(expert_offsets, E, blockIdx.y, tile)) return;
   const int lane = threadIdx.x & (WAVE_SIZE - 1);
   const int wave = threadIdx.x / WAVE_SIZE;
   const int n0 = blockIdx.x * MOE_NT + 16 * wave;
@@ -294,7 +304,7 @@ __global__ __launch_bounds__(256, 2) void moe_down_kernel(
     const int* __restrict__ sorted_slots,
     const int TK, const int E, const int H, const int I) {
   MoeTile tile;
-  if (!moe_find_tile(expert_offsets, E, blockIdx.y, tile)) return;
+  if (!moe_find_tile<MOE_BM>(expert_offsets, E, blockIdx.y, tile)) return;
   const int lane = threadIdx.x & (WAVE_SIZE - 1);
   const int wave = threadIdx.x / WAVE_SIZE;
   const int sk = blockIdx.z;
@@ -390,6 +400,273 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(
   for (int j = 0; j < 4; ++j) dst[j] = f2bf(acc[j]);
 }
 
+// ------------------------------------------------- tiled grouped GEMMs
+//
+// The compute-shaped family for many rows per expert. One workgroup of four
+// waves owns 128 sorted rows × 128 W rows of one expert and walks K in steps
+// of 64. Per step all 256 threads stage the A tile (128 × 64 bf16) and the W
+// tile (128 × 64 bf16) into LDS with 16-byte global loads; the waves, laid
+// out 2 × 2, read their MFMA fragments from there. So a W element is fetched
+// from memory once per 128 rows (the streaming kernels: once per 64) and an
+// A element once per workgroup (there: once per wave and n-tile).
+//
+// Schedule: two LDS buffers, one barrier per step. The global loads of step
+// k+1 are issued into registers before the MFMAs of step k and committed to
+// the other buffer after them; the barrier that ends step k both publishes
+// that buffer and retires the reads of step k's. (One buffer would need a
+// second barrier per step between the last fragment read and the commit.)
+//
+// Dead rows — A rows past tile.rows or with p ≥ T·K, W rows past the last
+// column — are never loaded: their staging registers stay zero and zeros go
+// to LDS. Their row pointer is row 0 of an in-bounds block and is not
+// dereferenced; a token index is clamped into [0, T-1] as in the streaming
+// kernel.
+
+#define MOE_TBM 128     // sorted rows per tiled m-tile (2 waves × 4 subtiles)
+#define MOE_TBN 128     // W rows per tiled workgroup (2 waves × 4 subtiles)
+#define MOE_TBK 64      // K elements staged per step (2 MFMA k-steps)
+// LDS row stride in dwords: 32 of data (64 bf16) + 4 of pad = 144 bytes, so
+// every 16-byte access stays aligned. Fragment read (ds_read_b128): lane l
+// reads the 4 dwords at 36·row + 16·kk + 4·(l >> 4), row = subtile base +
+// (l & 15). A subtile base is a multiple of 16 rows = 576 dwords = 9·64, no
+// bank shift. The 16 lanes of one k-group start at banks 36·r mod 64 = 0,
+// 36, 8, 44, 16, 52, 24, 60, 32, 4, 40, 12, 48, 20, 56, 28 for r = 0..15:
+// 36 = 4·9 with 9 odd, so r → 9r mod 16 is a bijection and the sixteen
+// 4-dword runs tile the 64 banks exactly once — conflict-free; the same
+// holds for any 8 consecutive rows on 32 banks. Without the pad (stride 32)
+// rows r and r + 2 would share their banks, an 8-way conflict.
+// Staging write (ds_write_b128): thread t writes chunk t & 7 of row t >> 3,
+// so 16 lanes cover two rows, banks [0, 32) and [36, 68) mod 64: one chunk
+// in sixteen meets a 2-way conflict, which is accepted.
+#define MOE_TROW_DW 36
+#define MOE_TTILE_DW (128 * MOE_TROW_DW)   // one 128-row tile
+#define MOE_TBUF_DW (2 * MOE_TTILE_DW)     // A tile + W tile
+#define MOE_TLDS_DW (2 * MOE_TBUF_DW)      // two buffers: 73728 bytes
+
+// K loop of one tiled workgroup. Thread t stages chunk t & 7 (8 bf16) of the
+// tile rows (t >> 3) + 32·j, j = 0..3, of A and of W: a_src / w_src point at
+// that chunk at k = 0 (always in bounds), *_live says whether the row is
+// loaded at all. Wave (wm, wn) accumulates tile rows 64·wm .. + 64 against
+// four 16-row W subtiles: LDS W rows 64·wn + 16·ns of a plain tile (down),
+// or, when the tile stacks 64 gate rows on the matching 64 up rows
+// (GATE_UP), gate rows 32·wn + 16·(ns & 1) for ns < 2 and the same up rows
+// (+ 64) for ns ≥ 2. mt = live 16-row A subtiles of this wave (0..4).
+template <bool GATE_UP>
+__device__ __forceinline__ void moe_tiled_mainloop(
+    moe_f32x4 (&acc)[4][4], const bf16* const (&a_src)[4],
+    const bool (&a_live)[4], const bf16* const (&w_src)[4],
+    const bool (&w_live)[4], const int kdim, const int mt,
+    unsigned int* lds) {
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE_SIZE - 1);
+  const int wm = tid / (2 * WAVE_SIZE);
+  const int wn = (tid / WAVE_SIZE) & 1;
+
+  uint4 ra[4], rw[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    ra[j] = make_uint4(0u, 0u, 0u, 0u);
+    rw[j] = make_uint4(0u, 0u, 0u, 0u);
+  }
+  auto fetch = [&](const int k0) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (a_live[j]) ra[j] = *reinterpret_cast<const uint4*>(a_src[j] + k0);
+      if (w_live[j]) rw[j] = *reinterpret_cast<const uint4*>(w_src[j] + k0);
+    }
+  };
+  const int stage_dw = (tid >> 3) * MOE_TROW_DW + (tid & 7) * 4;
+  auto commit = [&](unsigned int* buf) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      unsigned int* dst = buf + stage_dw + 32 * j * MOE_TROW_DW;
+      *reinterpret_cast<uint4*>(dst) = ra[j];
+      *reinterpret_cast<uint4*>(dst + MOE_TTILE_DW) = rw[j];
+    }
+  };
+
+  // same lane→k bijection for A and B: k-group lane/16 of each 32-k step
+  const int frag_dw = (lane & 15) * MOE_TROW_DW + (lane >> 4) * 4;
+  const int a_dw = 64 * wm * MOE_TROW_DW + frag_dw;
+  int w_dw[4];
+#pragma unroll
+  for (int ns = 0; ns < 4; ++ns) {
+    const int w_row = GATE_UP ? 64 * (ns >> 1) + 32 * wn + 16 * (ns & 1)
+                              : 64 * wn + 16 * ns;
+    w_dw[ns] = MOE_TTILE_DW + w_row * MOE_TROW_DW + frag_dw;
+  }
+
+  fetch(0);
+  commit(lds);
+  __syncthreads();
+  const int nk = kdim / MOE_TBK;
+  for (int kb = 0; kb < nk; ++kb) {
+    const unsigned int* cur = lds + (kb & 1) * MOE_TBUF_DW;
+    const bool more = kb + 1 < nk;  // uniform
+    if (more) fetch((kb + 1) * MOE_TBK);
+#pragma unroll
+    for (int kk = 0; kk < MOE_TBK / 32; ++kk) {
+      moe_bf16x8 b_frag[4];
+#pragma unroll
+      for (int ns = 0; ns < 4; ++ns) {
+        b_frag[ns] =
+            *reinterpret_cast<const moe_bf16x8*>(cur + w_dw[ns] + 16 * kk);
+      }
+#pragma unroll
+      for (int pm = 0; pm < 4; ++pm) {
+        if (pm >= mt) break;
+        const moe_bf16x8 a_frag = *reinterpret_cast<const moe_bf16x8*>(
+            cur + a_dw + 16 * pm * MOE_TROW_DW + 16 * kk);
+#pragma unroll
+        for (int ns = 0; ns < 4; ++ns) {
+          acc[pm][ns] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a_frag, b_frag[ns], acc[pm][ns], 0, 0, 0);
+        }
+      }
+    }
+    if (more) commit(lds + ((kb + 1) & 1) * MOE_TBUF_DW);
+    __syncthreads();
+  }
+}
+
+// The tiled gate_up + SwiGLU: tile = 128 sorted rows × 64 act columns, i.e.
+// 64 gate rows (LDS W rows 0..63) and the matching 64 up rows (64..127) of
+// the stacked [E, 2I, H] weight, so SwiGLU runs on the accumulators exactly
+// as in moe_gate_up_swiglu_kernel. grid = (ceil(I/64), tiled m_tiles).
+__global__ NO_PACKED_FP32 __launch_bounds__(256, 2) void
+moe_gate_up_swiglu_tiled_kernel(
+    bf16* __restrict__ act,               // [T*K, I]
+    const bf16* __restrict__ x,           // [T, H]
+    const bf16* __restrict__ w,           // [E, 2I, H]
+    const int* __restrict__ expert_offsets,
+    const int* __restrict__ sorted_slots,
+    const int T, const int E, const int top_k, const int H, const int I) {
+  MoeTile tile;
+  if (!moe_find_tile<MOE_TBM>(expert_offsets, E, blockIdx.y, tile)) return;
+  __shared__ __attribute__((aligned(16))) unsigned int lds[MOE_TLDS_DW];
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE_SIZE - 1);
+  const int wm = tid / (2 * WAVE_SIZE);
+  const int wn = (tid / WAVE_SIZE) & 1;
+  const int n0 = blockIdx.x * (MOE_TBN / 2);  // < I by the grid
+  const int TK = T * top_k;
+
+  const bf16* w_e = w + (long)tile.expert * 2 * I * H;
+  const int c8 = (tid & 7) * 8;
+  const bf16* a_src[4];
+  const bf16* w_src[4];
+  bool a_live[4], w_live[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int r = (tid >> 3) + 32 * j;
+    const int p = tile.row0 + r;
+    a_live[j] = r < tile.rows && p < TK;
+    // the gather: sorted position → slot → token row of x
+    const int slot = a_live[j] ? sorted_slots[p] : 0;
+    const int token = min(max(slot / top_k, 0), T - 1);
+    a_src[j] = x + (long)token * H + c8;
+    const int n = n0 + (r & 63);
+    w_live[j] = n < I;
+    w_src[j] = w_e + ((long)(w_live[j] ? n : 0) + (r >= 64 ? I : 0)) * H + c8;
+  }
+
+  moe_f32x4 acc[4][4];
+#pragma unroll
+  for (int pm = 0; pm < 4; ++pm)
+#pragma unroll
+    for (int ns = 0; ns < 4; ++ns)
+      acc[pm][ns] = moe_f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int mt = min(max((tile.rows - 64 * wm + 15) / 16, 0), 4);
+  moe_tiled_mainloop<true>(acc, a_src, a_live, w_src, w_live, H, mt, lds);
+
+#pragma unroll
+  for (int pm = 0; pm < 4; ++pm) {
+    if (pm >= mt) break;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = 64 * wm + 16 * pm + (lane >> 4) * 4 + i;
+      const int p = tile.row0 + m;
+      if (m >= tile.rows || p >= TK) continue;
+#pragma unroll
+      for (int ns = 0; ns < 2; ++ns) {
+        const int n_out = n0 + 32 * wn + 16 * ns + (lane & 15);
+        if (n_out >= I) continue;  // I % 16 == 0: uniform per subtile
+        const float g = acc[pm][ns][i];
+        const float u = acc[pm][2 + ns][i];
+        act[(long)p * I + n_out] = f2bf(g / (1.0f + expf(-g)) * u);
+      }
+    }
+  }
+}
+
+// The tiled down GEMM: tile = 128 sorted rows × 128 columns of H, K over I,
+// no gather (act is already sorted), no split-K: fp32 rows go to
+// ws[slot(p)] and moe_combine_kernel runs with SK = 1, so the sum order is
+// fixed. grid = (ceil(H/128), tiled m_tiles).
+__global__ NO_PACKED_FP32 __launch_bounds__(256, 2) void
+moe_down_tiled_kernel(
+    float* __restrict__ ws,               // [T*K, H]
+    const bf16* __restrict__ act,         // [T*K, I]
+    const bf16* __restrict__ w,           // [E, H, I]
+    const int* __restrict__ expert_offsets,
+    const int* __restrict__ sorted_slots,
+    const int TK, const int E, const int H, const int I) {
+  MoeTile tile;
+  if (!moe_find_tile<MOE_TBM>(expert_offsets, E, blockIdx.y, tile)) return;
+  __shared__ __attribute__((aligned(16))) unsigned int lds[MOE_TLDS_DW];
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE_SIZE - 1);
+  const int wm = tid / (2 * WAVE_SIZE);
+  const int wn = (tid / WAVE_SIZE) & 1;
+  const int n0 = blockIdx.x * MOE_TBN;  // < H by the grid
+
+  const bf16* w_e = w + (long)tile.expert * H * I;
+  const int c8 = (tid & 7) * 8;
+  const bf16* a_src[4];
+  const bf16* w_src[4];
+  bool a_live[4], w_live[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int r = (tid >> 3) + 32 * j;
+    const int p = tile.row0 + r;
+    a_live[j] = r < tile.rows && p < TK;
+    a_src[j] = act + (long)(a_live[j] ? p : 0) * I + c8;
+    const int n = n0 + r;
+    w_live[j] = n < H;
+    w_src[j] = w_e + (long)(w_live[j] ? n : 0) * I + c8;
+  }
+
+  moe_f32x4 acc[4][4];
+#pragma unroll
+  for (int pm = 0; pm < 4; ++pm)
+#pragma unroll
+    for (int ns = 0; ns < 4; ++ns)
+      acc[pm][ns] = moe_f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int mt = min(max((tile.rows - 64 * wm + 15) / 16, 0), 4);
+  moe_tiled_mainloop<false>(acc, a_src, a_live, w_src, w_live, I, mt, lds);
+
+#pragma unroll
+  for (int pm = 0; pm < 4; ++pm) {
+    if (pm >= mt) break;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = 64 * wm + 16 * pm + (lane >> 4) * 4 + i;
+      const int p = tile.row0 + m;
+      if (m >= tile.rows || p >= TK) continue;
+      const int slot = sorted_slots[p];
+      if (slot < 0 || slot >= TK) continue;
+      float* dst = ws + (long)slot * H;
+#pragma unroll
+      for (int ns = 0; ns < 4; ++ns) {
+        const int n_out = n0 + 64 * wn + 16 * ns + (lane & 15);
+        if (n_out < H) dst[n_out] = acc[pm][ns][i];
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------ launchers
 
 // Static upper bound on non-empty m-tiles: Σ_e ceil(n_e/BM) ≤ TK/BM + E
@@ -397,6 +674,22 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(
 extern "C" int moe_num_m_tiles(int TK, int E) {
   const int bound = TK / MOE_BM + E;
   return TK < bound ? TK : bound;
+}
+
+// The same bound for the 128-row m-tiles of the tiled kernels.
+extern "C" int moe_num_m_tiles_tiled(int TK, int E) {
+  const int bound = TK / MOE_TBM + E;
+  return TK < bound ? TK : bound;
+}
+
+// Which family a call with no forced variant runs: tiled once the experts
+// own MOE_TILED_MIN_ROWS sorted rows each on average. Static shapes only.
+// Never below 128 rows per expert (less than one full tiled m-tile each);
+// above that the threshold is the measured one, see docs/mi355x-kernels.md
+// "Tiled grouped GEMMs" and profiles/moe_tiled_ab.json.
+#define MOE_TILED_MIN_ROWS 128
+extern "C" int moe_use_tiled(int TK, int E) {
+  return (long)TK >= (long)MOE_TILED_MIN_ROWS * E ? 1 : 0;
 }
 
 // n-subtiles per wave in the down GEMM: 2 once an expert can own more
@@ -431,36 +724,52 @@ extern "C" void launch_moe_gate_up_swiglu(void* act, const void* x,
                                           const int* expert_offsets,
                                           const int* sorted_slots, int T,
                                           int E, int top_k, int H, int I,
-                                          hipStream_t stream) {
+                                          int tiled, hipStream_t stream) {
+  if (tiled) {
+    dim3 grid((I + MOE_TBN / 2 - 1) / (MOE_TBN / 2),
+              moe_num_m_tiles_tiled(T * top_k, E));
+    hipLaunchKernelGGL(moe_gate_up_swiglu_tiled_kernel, grid, dim3(256), 0,
+                       stream, (bf16*)act, (const bf16*)x, (const bf16*)w,
+                       expert_offsets, sorted_slots, T, E, top_k, H, I);
+    return;
+  }
   dim3 grid((I + MOE_NT - 1) / MOE_NT, moe_num_m_tiles(T * top_k, E));
   hipLaunchKernelGGL(moe_gate_up_swiglu_kernel, grid, dim3(256), 0, stream,
                      (bf16*)act, (const bf16*)x, (const bf16*)w,
                      expert_offsets, sorted_slots, T, E, top_k, H, I);
 }
 
+// tiled: num_splits must be 1 (the tiled kernel does not split K).
 extern "C" void launch_moe_down_combine(void* out, float* ws,
                                         const void* act, const void* w,
                                         const float* topk_w,
                                         const int* expert_offsets,
                                         const int* sorted_slots, int T,
                                         int E, int top_k, int H, int I,
-                                        int num_splits,
+                                        int num_splits, int tiled,
                                         hipStream_t stream) {
   const int TK = T * top_k;
-  const int nsub = moe_down_nsub(TK);
-  const int nt = MOE_NT * nsub;
-  dim3 grid((H + nt - 1) / nt, moe_num_m_tiles(TK, E), num_splits);
-  if (nsub == 1) {
-    hipLaunchKernelGGL((moe_down_kernel<1>), grid, dim3(256), 0, stream, ws,
+  if (tiled) {
+    dim3 grid((H + MOE_TBN - 1) / MOE_TBN, moe_num_m_tiles_tiled(TK, E));
+    hipLaunchKernelGGL(moe_down_tiled_kernel, grid, dim3(256), 0, stream, ws,
                        (const bf16*)act, (const bf16*)w, expert_offsets,
                        sorted_slots, TK, E, H, I);
   } else {
-    hipLaunchKernelGGL((moe_down_kernel<2>), grid, dim3(256), 0, stream, ws,
-                       (const bf16*)act, (const bf16*)w, expert_offsets,
-                       sorted_slots, TK, E, H, I);
+    const int nsub = moe_down_nsub(TK);
+    const int nt = MOE_NT * nsub;
+    dim3 grid((H + nt - 1) / nt, moe_num_m_tiles(TK, E), num_splits);
+    if (nsub == 1) {
+      hipLaunchKernelGGL((moe_down_kernel<1>), grid, dim3(256), 0, stream, ws,
+                         (const bf16*)act, (const bf16*)w, expert_offsets,
+                         sorted_slots, TK, E, H, I);
+    } else {
+      hipLaunchKernelGGL((moe_down_kernel<2>), grid, dim3(256), 0, stream, ws,
+                         (const bf16*)act, (const bf16*)w, expert_offsets,
+                         sorted_slots, TK, E, H, I);
+    }
   }
   const long n4 = (long)T * (H / 4);
   hipLaunchKernelGGL(moe_combine_kernel, dim3((n4 + 255) / 256), dim3(256),
                      0, stream, (bf16*)out, (const float*)ws, topk_w, T,
-                     top_k, H, num_splits);
+                     top_k, H, tiled ? 1 : num_splits);
 }

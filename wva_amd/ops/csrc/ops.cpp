@@ -603,6 +603,15 @@ void check_moe_sizes(long T, long E, long K) {
               "too many m-tiles for one launch");
 }
 
+// Kernel family of the two GEMMs: absent = the static-shape rule
+// (moe_use_tiled), else "stream" or "tiled". Python validates the string.
+int moe_tiled_arg(const c10::optional<std::string>& variant, long TK, long E) {
+  if (!variant.has_value()) return moe_use_tiled((int)TK, (int)E);
+  TORCH_CHECK(*variant == "stream" || *variant == "tiled",
+              "variant must be \"stream\" or \"tiled\"");
+  return *variant == "tiled" ? 1 : 0;
+}
+
 // router_logits fp32 [T, E] → (topk_idx [T,K] i32, topk_w [T,K] f32,
 // expert_offsets [E+1] i32, sorted_slots [T*K] i32), all on device.
 std::vector<torch::Tensor> moe_route(torch::Tensor router_logits,
@@ -633,7 +642,8 @@ std::vector<torch::Tensor> moe_route(torch::Tensor router_logits,
 // expert-sorted order. w_gate_up is the stacked [E, 2I, H] tensor.
 torch::Tensor moe_gate_up_swiglu(torch::Tensor x, torch::Tensor w_gate_up,
                                  torch::Tensor expert_offsets,
-                                 torch::Tensor sorted_slots, int64_t top_k) {
+                                 torch::Tensor sorted_slots, int64_t top_k,
+                                 c10::optional<std::string> variant) {
   check_bf16_contig(x, "x");
   check_bf16_contig(w_gate_up, "w_gate_up");
   check_i32_contig(expert_offsets, "expert_offsets");
@@ -657,17 +667,22 @@ torch::Tensor moe_gate_up_swiglu(torch::Tensor x, torch::Tensor w_gate_up,
                             w_gate_up.data_ptr(),
                             expert_offsets.data_ptr<int>(),
                             sorted_slots.data_ptr<int>(), (int)T, (int)E,
-                            (int)top_k, (int)H, (int)I, current_stream());
+                            (int)top_k, (int)H, (int)I,
+                            moe_tiled_arg(variant, T * top_k, E),
+                            current_stream());
   return act;
 }
 
 // out [T, H] = Σ_k topk_w[t,k] · (act_sorted[pos(t,k)] · w_down[e]^T),
 // w_down the stacked [E, H, I] tensor; split-K partials go through an
-// fp32 workspace indexed by slot and are summed in a fixed order.
+// fp32 workspace indexed by slot and are summed in a fixed order. The
+// tiled kernels do not split K: their workspace is T·K·H floats, refused
+// above 1 GiB (the cap of the ragged extend workspace).
 torch::Tensor moe_down_combine(torch::Tensor act_sorted, torch::Tensor w_down,
                                torch::Tensor topk_w,
                                torch::Tensor expert_offsets,
-                               torch::Tensor sorted_slots) {
+                               torch::Tensor sorted_slots,
+                               c10::optional<std::string> variant) {
   check_bf16_contig(act_sorted, "act_sorted");
   check_bf16_contig(w_down, "w_down");
   check_i32_contig(expert_offsets, "expert_offsets");
@@ -689,7 +704,11 @@ torch::Tensor moe_down_combine(torch::Tensor act_sorted, torch::Tensor w_down,
   TORCH_CHECK(H % 16 == 0, "H (N-dim) must be a multiple of 16");
   TORCH_CHECK(expert_offsets.numel() == E + 1, "expert_offsets must be [E+1]");
   TORCH_CHECK(sorted_slots.numel() == T * K, "sorted_slots must be [T*K]");
-  const int sk = moe_down_num_splits((int)(T * K), (int)E, (int)H, (int)I);
+  const int tiled = moe_tiled_arg(variant, T * K, E);
+  const int sk =
+      tiled ? 1 : moe_down_num_splits((int)(T * K), (int)E, (int)H, (int)I);
+  TORCH_CHECK(!tiled || T * K * H <= (1L << 28),
+              "tiled down workspace would exceed 1 GiB");
   auto ws = torch::empty({(long)sk * T * K * H},
                          act_sorted.options().dtype(torch::kFloat32));
   auto out = torch::empty({T, H}, act_sorted.options());
@@ -698,7 +717,8 @@ torch::Tensor moe_down_combine(torch::Tensor act_sorted, torch::Tensor w_down,
                           topk_w.data_ptr<float>(),
                           expert_offsets.data_ptr<int>(),
                           sorted_slots.data_ptr<int>(), (int)T, (int)E,
-                          (int)K, (int)H, (int)I, sk, current_stream());
+                          (int)K, (int)H, (int)I, sk, tiled,
+                          current_stream());
   return out;
 }
 
@@ -706,6 +726,10 @@ int64_t moe_down_splits(int64_t tokens, int64_t top_k, int64_t num_experts,
                         int64_t hidden, int64_t inter) {
   return moe_down_num_splits((int)(tokens * top_k), (int)num_experts,
                              (int)hidden, (int)inter);
+}
+
+bool moe_rule_tiled(int64_t tokens, int64_t top_k, int64_t num_experts) {
+  return moe_use_tiled((int)(tokens * top_k), (int)num_experts) != 0;
 }
 
 }  // namespace
@@ -799,13 +823,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_gate_up_swiglu", &moe_gate_up_swiglu,
         "Grouped gate_up GEMM + SwiGLU over expert-sorted rows",
         py::arg("x"), py::arg("w_gate_up"), py::arg("expert_offsets"),
-        py::arg("sorted_slots"), py::arg("top_k"));
+        py::arg("sorted_slots"), py::arg("top_k"),
+        py::arg("variant") = py::none());
   m.def("moe_down_combine", &moe_down_combine,
         "Grouped down GEMM + deterministic top-k combine",
         py::arg("act_sorted"), py::arg("w_down"), py::arg("topk_w"),
-        py::arg("expert_offsets"), py::arg("sorted_slots"));
+        py::arg("expert_offsets"), py::arg("sorted_slots"),
+        py::arg("variant") = py::none());
   m.def("moe_down_splits", &moe_down_splits,
         "Split-K factor moe_down_combine uses for these static shapes",
         py::arg("tokens"), py::arg("top_k"), py::arg("num_experts"),
         py::arg("hidden"), py::arg("inter"));
+  m.def("moe_rule_tiled", &moe_rule_tiled,
+        "Whether the MoE GEMMs take the tiled kernels for these static "
+        "shapes when no variant is forced",
+        py::arg("tokens"), py::arg("top_k"), py::arg("num_experts"));
 }
