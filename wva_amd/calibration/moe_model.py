@@ -16,6 +16,8 @@ because decode MoE is weight-streaming-bound and the sparse gather path's
 per-expert `nonzero()` syncs dominate. `moe_impl="grouped"` instead routes
 on the device and multiplies only the routed (token, expert) pairs
 (ops.moe_mlp, csrc/moe.hip): what a serving engine's fused MoE does.
+With `weights_dtype="fp8"` that path keeps the experts (≈ 90 of the 94 GB)
+as weight-only e4m3 with per-row scales and nothing in bf16.
 """
 from __future__ import annotations
 
@@ -65,10 +67,18 @@ TINY_MOE = MixtralConfig(
 
 
 class _MoELayer(blocks.AttnLayer):
-    def __init__(self, cfg: MixtralConfig, device, dtype, gen):
+    def __init__(self, cfg: MixtralConfig, device, dtype, gen, fp8=False):
         h, inter = cfg.hidden_size, cfg.intermediate_size
         super().__init__(h, cfg.q_size, cfg.kv_size, device, dtype, gen)
         self.w_router = blocks.w(cfg.num_experts, h, device, dtype, gen)
+        if fp8:
+            # same draws in the same order as below, quantised expert by
+            # expert: a layer never holds a second, bf16 copy of its experts
+            self.w_gate_up_stacked, self.w_gate_up_scale = self._draw_fp8(
+                cfg.num_experts, 2 * inter, h, device, dtype, gen)
+            self.w_down_stacked, self.w_down_scale = self._draw_fp8(
+                cfg.num_experts, h, inter, device, dtype, gen)
+            return
         self.set_expert_weights(
             torch.stack([
                 blocks.w(2 * inter, h, device, dtype, gen)
@@ -80,6 +90,23 @@ class _MoELayer(blocks.AttnLayer):
             ]),
         )
 
+    @staticmethod
+    def _draw_fp8(num_experts, rows, cols, device, dtype, gen):
+        """(e4m3 stack [E, rows, cols], fp32 scales [E, rows]) of seeded
+        expert weights (ops.quantize_moe_weights)."""
+        q = torch.empty(
+            num_experts, rows, cols, device=device, dtype=torch.float8_e4m3fn
+        )
+        scale = torch.empty(
+            num_experts, rows, device=device, dtype=torch.float32
+        )
+        for e in range(num_experts):
+            q_e, s_e = ops.quantize_moe_weights(
+                blocks.w(rows, cols, device, dtype, gen).unsqueeze(0)
+            )
+            q[e], scale[e] = q_e[0], s_e[0]
+        return q, scale
+
     def set_expert_weights(self, gate_up_stacked, down_stacked) -> None:
         """Replace expert weights, recomputing every derived operand
         (tests copy weights between devices through this)."""
@@ -89,6 +116,7 @@ class _MoELayer(blocks.AttnLayer):
         # sparse reference path
         self.w_gate_up_stacked = gate_up_stacked
         self.w_down_stacked = down_stacked
+        self.w_gate_up_scale = self.w_down_scale = None  # bf16 operands
         self.w_gate_up = list(gate_up_stacked)
         self.w_down = list(down_stacked)
         # dense-path operands (no transposed VIEWS at run time — hipBLASLt
@@ -126,13 +154,28 @@ class MixtralDecodeModel:
         seed: int = 0,
         kv_dtype: str = "bf16",
         moe_impl: str = "auto",
+        weights_dtype: str = "bf16",
     ):
         if moe_impl not in MOE_IMPLS:
             raise ValueError(
                 f"moe_impl must be one of {MOE_IMPLS}, got {moe_impl!r}"
             )
+        if weights_dtype not in ("bf16", "fp8"):
+            raise ValueError(
+                f'weights_dtype must be "bf16" or "fp8", got {weights_dtype!r}'
+            )
+        if weights_dtype == "fp8" and moe_impl != "grouped":
+            # the dense and sparse paths multiply bf16 operands; keeping a
+            # bf16 copy for them would give the halved memory back
+            raise ValueError(
+                'weights_dtype="fp8" needs moe_impl="grouped", got '
+                f"{moe_impl!r}"
+            )
         self.cfg = cfg
         self.moe_impl = moe_impl
+        # "fp8": weight-only e4m3 expert stacks with per-row scales (W8A16,
+        # ops.moe_mlp); attention, router, embeddings and lm_head stay bf16
+        self.weights_dtype = weights_dtype
         self.device = torch.device(device)
         self.dtype = torch.bfloat16
         self.kv_dtype = kv_dtype
@@ -146,7 +189,10 @@ class MixtralDecodeModel:
 
         draw = (self.device, self.dtype, gen)
         self.embed = blocks.w(cfg.vocab_size, cfg.hidden_size, *draw)
-        self.layers = [_MoELayer(cfg, *draw) for _ in range(cfg.num_layers)]
+        self.layers = [
+            _MoELayer(cfg, *draw, fp8=weights_dtype == "fp8")
+            for _ in range(cfg.num_layers)
+        ]
         self.final_norm = torch.ones(
             cfg.hidden_size, device=self.device, dtype=self.dtype
         )
@@ -194,6 +240,8 @@ class MixtralDecodeModel:
             return ops.moe_mlp(
                 h2, router_logits, layer.w_gate_up_stacked,
                 layer.w_down_stacked, cfg.top_k,
+                w_gate_up_scale=layer.w_gate_up_scale,
+                w_down_scale=layer.w_down_scale,
             )
         weights, selected = torch.topk(router_logits, cfg.top_k, dim=-1)
         weights = torch.softmax(weights, dim=-1).to(h2.dtype)  # [B, K]

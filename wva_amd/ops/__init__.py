@@ -274,15 +274,37 @@ def moe_route_ref(router_logits: torch.Tensor, top_k: int):
     )
 
 
+def quantize_moe_weights(w: torch.Tensor):
+    """Stacked expert weights [E, N, K] → (q float8_e4m3fn [E, N, K], scale
+    fp32 [E, N]) with w ≈ q · scale[:, :, None]: one scale per (expert,
+    output row), amax_row / 448 (1.0 for an all-zero row). The quotient is
+    clamped to ±448 before the cast, which would turn anything past 464
+    into NaN."""
+    wf = w.float()
+    amax = wf.abs().amax(dim=-1)
+    scale = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax))
+    q = (wf / scale.unsqueeze(-1)).clamp(-448.0, 448.0)
+    return q.to(torch.float8_e4m3fn), scale
+
+
+def _moe_expert_f32(w, w_scale, e: int) -> torch.Tensor:
+    """Expert e of a stacked weight in float32, dequantised when scaled."""
+    if w_scale is None:
+        return w[e].float()
+    return w[e].float() * w_scale[e].float().unsqueeze(-1)
+
+
 def moe_gate_up_swiglu_ref(
     x: torch.Tensor,
     w_gate_up: torch.Tensor,
     expert_offsets: torch.Tensor,
     sorted_slots: torch.Tensor,
     top_k: int,
+    w_scale: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """fp32 [T*K, I]: silu(g)*u of x[slot // K] @ w_gate_up[e].T for the
-    expert e owning each sorted position; w_gate_up is [E, 2I, H]."""
+    expert e owning each sorted position; w_gate_up is [E, 2I, H], times
+    w_scale [E, 2I] row by row when that is given."""
     E, two_i, _ = w_gate_up.shape
     inter = two_i // 2
     offs = expert_offsets.tolist()
@@ -294,7 +316,8 @@ def moe_gate_up_swiglu_ref(
         lo, hi = offs[e], offs[e + 1]
         if hi == lo:
             continue
-        gu = x[tokens[lo:hi]].float() @ w_gate_up[e].float().t()
+        w_e = _moe_expert_f32(w_gate_up, w_scale, e)
+        gu = x[tokens[lo:hi]].float() @ w_e.t()
         out[lo:hi] = torch.nn.functional.silu(gu[:, :inter]) * gu[:, inter:]
     return out
 
@@ -305,9 +328,11 @@ def moe_down_combine_ref(
     topk_w: torch.Tensor,
     expert_offsets: torch.Tensor,
     sorted_slots: torch.Tensor,
+    w_scale: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """fp32 [T, H]: sum_k topk_w[t,k] * (act_sorted[pos(t,k)] @
-    w_down[e].T); w_down is [E, H, I]."""
+    w_down[e].T); w_down is [E, H, I], times w_scale [E, H] row by row when
+    that is given."""
     E, hidden, _ = w_down.shape
     T, K = topk_w.shape
     offs = expert_offsets.tolist()
@@ -317,7 +342,8 @@ def moe_down_combine_ref(
         lo, hi = offs[e], offs[e + 1]
         if hi == lo:
             continue
-        y[slots[lo:hi]] = act_sorted[lo:hi].float() @ w_down[e].float().t()
+        w_e = _moe_expert_f32(w_down, w_scale, e)
+        y[slots[lo:hi]] = act_sorted[lo:hi].float() @ w_e.t()
     return (y.reshape(T, K, hidden) * topk_w.float().unsqueeze(-1)).sum(dim=1)
 
 
@@ -327,13 +353,18 @@ def moe_mlp_ref(
     w_gate_up: torch.Tensor,
     w_down: torch.Tensor,
     top_k: int,
+    w_gate_up_scale: Optional[torch.Tensor] = None,
+    w_down_scale: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """fp32 routed expert MLP; `act` is rounded to bf16 between the two
-    GEMMs exactly as the kernels do."""
+    GEMMs exactly as the kernels do. The scales as in the two references
+    it is made of."""
     _, topk_w, offsets, slots = moe_route_ref(router_logits, top_k)
-    act = moe_gate_up_swiglu_ref(x, w_gate_up, offsets, slots, top_k)
+    act = moe_gate_up_swiglu_ref(
+        x, w_gate_up, offsets, slots, top_k, w_gate_up_scale
+    )
     return moe_down_combine_ref(
-        act.to(torch.bfloat16), w_down, topk_w, offsets, slots
+        act.to(torch.bfloat16), w_down, topk_w, offsets, slots, w_down_scale
     )
 
 
@@ -565,6 +596,15 @@ def _check_moe_variant(variant):
         )
 
 
+def _check_moe_scaled(variant, *scales):
+    """fp8 expert weights (a scale is given) have no tiled kernels."""
+    if variant == "tiled" and any(s is not None for s in scales):
+        raise ValueError(
+            'variant="tiled" has no fp8 form: scaled (float8_e4m3fn) expert '
+            "weights run the streaming kernels only"
+        )
+
+
 def moe_variant(tokens: int, top_k: int, num_experts: int) -> str:
     """Kernel family the MoE GEMMs take for these static shapes when no
     variant is forced: "stream" (64-row m-tiles, weights streamed per
@@ -581,18 +621,26 @@ def moe_gate_up_swiglu(
     sorted_slots: torch.Tensor,
     top_k: int,
     variant: Optional[str] = None,
+    w_scale: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Grouped gate_up GEMM + SwiGLU over the routed rows only: bf16
     [T*K, I] in expert-sorted order, against the stacked [E, 2I, H].
     `variant` forces a kernel family (see moe_variant, which None
-    follows); the CPU reference has none and ignores it."""
+    follows); the CPU reference has none and ignores it.
+
+    With `w_scale` fp32 [E, 2I] the weights are weight-only fp8 (see
+    quantize_moe_weights): w_gate_up is float8_e4m3fn and stands for
+    w_gate_up * w_scale[:, :, None]; activations stay bf16. fp8 weights
+    run the streaming kernels at every T and refuse variant="tiled"."""
     _check_moe_variant(variant)
+    _check_moe_scaled(variant, w_scale)
     if x.is_cuda:
         return _require_ext().moe_gate_up_swiglu(
-            x, w_gate_up, expert_offsets, sorted_slots, top_k, variant
+            x, w_gate_up, expert_offsets, sorted_slots, top_k, variant,
+            w_scale,
         )
     return moe_gate_up_swiglu_ref(
-        x, w_gate_up, expert_offsets, sorted_slots, top_k
+        x, w_gate_up, expert_offsets, sorted_slots, top_k, w_scale
     ).to(x.dtype)
 
 
@@ -603,17 +651,21 @@ def moe_down_combine(
     expert_offsets: torch.Tensor,
     sorted_slots: torch.Tensor,
     variant: Optional[str] = None,
+    w_scale: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Grouped down GEMM against the stacked [E, H, I] + top-k combine:
-    bf16 [T, H], summed in a fixed order (deterministic). `variant` as in
+    bf16 [T, H], summed in a fixed order (deterministic). `variant` and
+    `w_scale` (fp32 [E, H] for float8_e4m3fn w_down) as in
     moe_gate_up_swiglu."""
     _check_moe_variant(variant)
+    _check_moe_scaled(variant, w_scale)
     if act_sorted.is_cuda:
         return _require_ext().moe_down_combine(
-            act_sorted, w_down, topk_w, expert_offsets, sorted_slots, variant
+            act_sorted, w_down, topk_w, expert_offsets, sorted_slots, variant,
+            w_scale,
         )
     return moe_down_combine_ref(
-        act_sorted, w_down, topk_w, expert_offsets, sorted_slots
+        act_sorted, w_down, topk_w, expert_offsets, sorted_slots, w_scale
     ).to(act_sorted.dtype)
 
 
@@ -636,21 +688,31 @@ def moe_mlp(
     w_down: torch.Tensor,
     top_k: int,
     variant: Optional[str] = None,
+    w_gate_up_scale: Optional[torch.Tensor] = None,
+    w_down_scale: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Routed expert MLP: x [T, H] bf16, router_logits [T, E] fp32,
     stacked expert weights [E, 2I, H] / [E, H, I] → bf16 [T, H].
 
     Only routed experts' weights are streamed and only routed tokens are
     multiplied; no step syncs with the host (csrc/moe.hip). `variant`
-    goes to both GEMMs; None follows moe_variant in each of them."""
+    goes to both GEMMs; None follows moe_variant in each of them. The two
+    scales go to the GEMM of their weight (weight-only fp8, see
+    moe_gate_up_swiglu); they stay on the device like everything else."""
     _check_moe_variant(variant)
+    _check_moe_scaled(variant, w_gate_up_scale, w_down_scale)
     if x.is_cuda:
         _, topk_w, offsets, slots = moe_route(router_logits, top_k)
-        act = moe_gate_up_swiglu(x, w_gate_up, offsets, slots, top_k, variant)
-        return moe_down_combine(
-            act, w_down, topk_w, offsets, slots, variant
+        act = moe_gate_up_swiglu(
+            x, w_gate_up, offsets, slots, top_k, variant, w_gate_up_scale
         )
-    return moe_mlp_ref(x, router_logits, w_gate_up, w_down, top_k).to(x.dtype)
+        return moe_down_combine(
+            act, w_down, topk_w, offsets, slots, variant, w_down_scale
+        )
+    return moe_mlp_ref(
+        x, router_logits, w_gate_up, w_down, top_k, w_gate_up_scale,
+        w_down_scale,
+    ).to(x.dtype)
 
 
 def enable_tuned_gemms() -> bool:

@@ -86,6 +86,28 @@ __device__ __forceinline__ float fp8_to_f32(fp8_t v) {
   return f[0];
 }
 
+// 8 adjacent e4m3 bytes (two dwords in memory order) -> the 8 bf16 of an MFMA
+// operand fragment, element i from byte i. Exact: every finite e4m3 value
+// (3 mantissa bits, |v| <= 448) is a bf16 value, so the upper half of each
+// converted fp32 IS its bf16 and the lower half is zero — no rounding, the
+// halves are only packed. The two NaN codes come out as some NaN.
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_vt;
+__device__ __forceinline__ bf16x8_frag fp8x8_to_bf16x8(unsigned int lo,
+                                                       unsigned int hi) {
+  const unsigned int src[2] = {lo, hi};
+  u32x4_vt out;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    const float2_vt f = (d & 1)
+        ? __builtin_amdgcn_cvt_pk_f32_fp8(src[d >> 1], true)
+        : __builtin_amdgcn_cvt_pk_f32_fp8(src[d >> 1], false);
+    // v_perm_b32: bytes 2, 3 of f[0] below bytes 2, 3 (selectors 6, 7) of f[1]
+    out[d] = __builtin_amdgcn_perm(__float_as_uint(f[1]),
+                                   __float_as_uint(f[0]), 0x07060302u);
+  }
+  return __builtin_bit_cast(bf16x8_frag, out);
+}
+
 // --- ragged chunked prefill: the clamps every kernel that reads the packed
 // rows applies (prefill_attention.hip, its merge, the chunk append of
 // rope.hip), so that all of them address the same rows whatever the device

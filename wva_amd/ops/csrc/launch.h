@@ -148,8 +148,12 @@ void launch_moe_route(int* topk_idx, float* topk_w, int* expert_offsets,
                       int* sorted_slots, const float* logits, int T, int E,
                       int K, hipStream_t stream);
 // act [T·top_k, I] = silu(g)·u of x [T, H] · w [E, 2I, H]^T, rows in
-// expert-sorted order. `tiled` picks the kernel family.
+// expert-sorted order. `tiled` picks the kernel family. w is bf16, or e4m3
+// with float scales w_scale [E, 2I], one per stacked row, when w_fp8 (w_scale
+// is null otherwise); fp8 weights always run the streaming family, whatever
+// `tiled` says.
 void launch_moe_gate_up_swiglu(void* act, const void* x, const void* w,
+                               const float* w_scale, int w_fp8,
                                const int* expert_offsets,
                                const int* sorted_slots, int T, int E,
                                int top_k, int H, int I, int tiled,
@@ -157,8 +161,10 @@ void launch_moe_gate_up_swiglu(void* act, const void* x, const void* w,
 // out [T, H] = Σ_k topk_w · (act · w [E, H, I]^T); `ws` holds
 // num_splits·T·top_k·H floats and is always used. With `tiled` num_splits
 // must be 1: the tiled kernel does not split K, ws is T·top_k·H floats.
+// w_scale [E, H] / w_fp8 as in launch_moe_gate_up_swiglu.
 void launch_moe_down_combine(void* out, float* ws, const void* act,
-                             const void* w, const float* topk_w,
+                             const void* w, const float* w_scale, int w_fp8,
+                             const float* topk_w,
                              const int* expert_offsets,
                              const int* sorted_slots, int T, int E, int top_k,
                              int H, int I, int num_splits, int tiled,

@@ -30,6 +30,13 @@
 // grouped GEMMs" below). moe_use_tiled picks the family from (T·K, E) alone;
 // route, sort and combine are common to both.
 //
+// The streaming family also takes weight-only fp8 experts (W8A16): e4m3
+// weights with one fp32 scale per (expert, output row), bf16 activations and
+// the same bf16 MFMA (moe_mma_stream_fp8 and the two *_fp8_kernel). The
+// scale is applied once, in fp32, to the accumulator; grids, splits,
+// workspace and combine are those of the bf16 call. The tiled family has no
+// fp8 form yet: fp8 weights stream at every T.
+//
 // Fragment convention as in skinny_gemm.hip: identical lane→k bijection
 // for A and B (a different one than skinny_gemm's, see moe_mma_stream);
 // C/D mapping col = lane&15 (n), row = (lane>>4)·4 + reg (m).
@@ -225,6 +232,72 @@ __device__ __forceinline__ void moe_mma_stream(
   }
 }
 
+// moe_mma_stream for weight-only fp8 (W8A16): W rows are e4m3 bytes, A rows
+// stay bf16, the MFMA is the same bf16 one. The bf16 lane→k map on 1-byte
+// elements would shrink the run that the four lanes of a W row read per
+// load instruction to 32 B. So the 128-k block is walked as two halves of
+// 64 k instead, and in half j k-group g = lane/16 owns the SIXTEEN elements
+// at 64·j + 16·g: W is one 16-byte load per live row — again one contiguous
+// 64 B run per row and instruction, with half as many load instructions per
+// block — and A the 16 bf16 at the same k as two adjacent 16-byte loads.
+// Elements 0..7 feed one MFMA and 8..15 the next, for A and B alike, so the
+// k-sum is exact as before. The raw e4m3 values are multiplied; the row
+// scale commutes with the k-sum and is the caller's epilogue.
+template <int NSUB>
+__device__ __forceinline__ void moe_mma_stream_fp8(
+    moe_f32x4 (&acc)[4][NSUB], const bf16* const (&a_rows)[4],
+    const bool (&a_live)[4], const fp8_t* const (&w_rows)[NSUB],
+    const bool (&n_live)[NSUB], const int mt, const int k_begin,
+    const int k_end, const int lane) {
+  const int lane_k = 16 * (lane / 16);
+  // the staggered, wrapping K start of moe_mma_stream
+  const int nkb = (k_end - k_begin) / MOE_KT;
+  int kb = (int)((blockIdx.x * 5 + blockIdx.y * 3) % nkb);
+  for (int it = 0; it < nkb; ++it) {
+    const int k0 = k_begin + kb * MOE_KT;
+    if (++kb == nkb) kb = 0;
+#pragma unroll
+    for (int j = 0; j < MOE_KT / 64; ++j) {
+      const int k = k0 + 64 * j + lane_k;
+      uint4 wq[NSUB];
+#pragma unroll
+      for (int ns = 0; ns < NSUB; ++ns) {
+        // e4m3 zero is the zero byte: a dead row converts to a zero fragment
+        wq[ns] = n_live[ns] ? *reinterpret_cast<const uint4*>(w_rows[ns] + k)
+                            : make_uint4(0u, 0u, 0u, 0u);
+      }
+      // one 8-element half at a time, so that only one converted B fragment
+      // per n-subtile is live next to the raw bytes of the other half
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        moe_bf16x8 b_frag[NSUB];
+#pragma unroll
+        for (int ns = 0; ns < NSUB; ++ns) {
+          b_frag[ns] = h == 0 ? fp8x8_to_bf16x8(wq[ns].x, wq[ns].y)
+                              : fp8x8_to_bf16x8(wq[ns].z, wq[ns].w);
+        }
+#pragma unroll
+        for (int pm = 0; pm < 4; ++pm) {
+          if (pm >= mt) break;
+          moe_bf16x8 a_frag;
+          if (a_live[pm]) {
+            a_frag =
+                *reinterpret_cast<const moe_bf16x8*>(a_rows[pm] + k + 8 * h);
+          } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) a_frag[i] = 0;
+          }
+#pragma unroll
+          for (int ns = 0; ns < NSUB; ++ns) {
+            acc[pm][ns] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                a_frag, b_frag[ns], acc[pm][ns], 0, 0, 0);
+          }
+        }
+      }
+    }
+  }
+}
+
 // act_sorted[p, n] = silu(g)·u with g = x[token(p)]·Wg[e][n], u = ...Wu[e][n].
 // Each wave owns 16 gate rows AND the matching 16 up rows (offset I) of
 // the stacked [E, 2I, H] weight, both multiplied against the same
@@ -285,6 +358,77 @@ __global__ __launch_bounds__(256, 2) void moe_gate_up_swiglu_kernel(
       if (m >= tile.rows || p >= TK) continue;
       const float g = acc[pm][0][i];
       const float u = acc[pm][1][i];
+      act[(long)p * I + n_out] = f2bf(g / (1.0f + expf(-g)) * u);
+    }
+  }
+}
+
+// moe_gate_up_swiglu_kernel for e4m3 weights with one fp32 scale per (expert,
+// stacked row), w_scale [E, 2I]: same grid, tile search, gather and SwiGLU. A
+// lane's output column is fixed, so it loads its gate and its up scale once,
+// before the K loop, and applies them in fp32 to the accumulators ahead of
+// SwiGLU. (Written out next to the bf16 kernel instead of sharing one
+// templated body with it: routed through a shared body the bf16 kernel no
+// longer compiled to the instructions it was measured with.)
+__global__ NO_PACKED_FP32 __launch_bounds__(256, 2) void
+moe_gate_up_swiglu_fp8_kernel(
+    bf16* __restrict__ act,               // [T*K, I]
+    const bf16* __restrict__ x,           // [T, H]
+    const fp8_t* __restrict__ w,          // [E, 2I, H] e4m3
+    const float* __restrict__ w_scale,    // [E, 2I]
+    const int* __restrict__ expert_offsets,
+    const int* __restrict__ sorted_slots,
+    const int T, const int E, const int top_k, const int H, const int I) {
+  MoeTile tile;
+  if (!moe_find_tile<MOE_BM>(expert_offsets, E, blockIdx.y, tile)) return;
+  const int lane = threadIdx.x & (WAVE_SIZE - 1);
+  const int wave = threadIdx.x / WAVE_SIZE;
+  const int n0 = blockIdx.x * MOE_NT + 16 * wave;
+  if (n0 >= I) return;  // I % 16 == 0: a wave's tile is all live or dead
+  const int TK = T * top_k;
+  const int n_out = n0 + (lane & 15);
+
+  const fp8_t* w_rows[2];
+  w_rows[0] = w + ((long)tile.expert * 2 * I + n_out) * H;
+  w_rows[1] = w_rows[0] + (long)I * H;
+  const bool n_live[2] = {true, true};
+  const float* scale_e = w_scale + (long)tile.expert * 2 * I + n_out;
+  const float scale_g = scale_e[0];
+  const float scale_u = scale_e[I];
+
+  const int mt = (tile.rows + 15) / 16;
+  const bf16* a_rows[4];
+  bool a_live[4];
+#pragma unroll
+  for (int pm = 0; pm < 4; ++pm) {
+    const int m = pm * 16 + (lane & 15);
+    const int p = tile.row0 + m;
+    a_live[pm] = m < tile.rows && p < TK;
+    // the gather: sorted position → slot → token row of x
+    const int slot = a_live[pm] ? sorted_slots[p] : 0;
+    const int token = min(max(slot / top_k, 0), T - 1);
+    a_rows[pm] = x + (long)token * H;
+  }
+
+  moe_f32x4 acc[4][2];
+#pragma unroll
+  for (int pm = 0; pm < 4; ++pm)
+#pragma unroll
+    for (int ns = 0; ns < 2; ++ns)
+      acc[pm][ns] = moe_f32x4{0.f, 0.f, 0.f, 0.f};
+
+  moe_mma_stream_fp8<2>(acc, a_rows, a_live, w_rows, n_live, mt, 0, H, lane);
+
+#pragma unroll
+  for (int pm = 0; pm < 4; ++pm) {
+    if (pm >= mt) break;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = pm * 16 + (lane >> 4) * 4 + i;
+      const int p = tile.row0 + m;
+      if (m >= tile.rows || p >= TK) continue;
+      const float g = scale_g * acc[pm][0][i];
+      const float u = scale_u * acc[pm][1][i];
       act[(long)p * I + n_out] = f2bf(g / (1.0f + expf(-g)) * u);
     }
   }
@@ -360,6 +504,83 @@ __global__ __launch_bounds__(256, 2) void moe_down_kernel(
       for (int ns = 0; ns < NSUB; ++ns) {
         const int n_out = n0 + 16 * ns + (lane & 15);
         if (n_out < H) dst[n_out] = acc[pm][ns][i];
+      }
+    }
+  }
+}
+
+// moe_down_kernel for e4m3 weights with w_scale [E, H]: same grid, splits and
+// workspace rows. The partial stored to ws is scale·acc (a row scale commutes
+// with the k-sum), so moe_combine_kernel and its sum order do not change. A
+// dead column takes scale 0 and, as there, is not stored.
+template <int NSUB>
+__global__ NO_PACKED_FP32 __launch_bounds__(256, 2) void moe_down_fp8_kernel(
+    float* __restrict__ ws,               // [SK, T*K, H]
+    const bf16* __restrict__ act,         // [T*K, I]
+    const fp8_t* __restrict__ w,          // [E, H, I] e4m3
+    const float* __restrict__ w_scale,    // [E, H]
+    const int* __restrict__ expert_offsets,
+    const int* __restrict__ sorted_slots,
+    const int TK, const int E, const int H, const int I) {
+  MoeTile tile;
+  if (!moe_find_tile<MOE_BM>(expert_offsets, E, blockIdx.y, tile)) return;
+  const int lane = threadIdx.x & (WAVE_SIZE - 1);
+  const int wave = threadIdx.x / WAVE_SIZE;
+  const int sk = blockIdx.z;
+  const int SK = gridDim.z;
+  const int n0 = blockIdx.x * MOE_NT * NSUB + 16 * NSUB * wave;
+  if (n0 >= H) return;  // H % 16 == 0
+
+  const fp8_t* w_rows[NSUB];
+  bool n_live[NSUB];
+  float scale[NSUB];
+#pragma unroll
+  for (int ns = 0; ns < NSUB; ++ns) {
+    const int n_row = n0 + 16 * ns + (lane & 15);
+    n_live[ns] = n_row < H;
+    const long row = (long)tile.expert * H + (n_live[ns] ? n_row : 0);
+    w_rows[ns] = w + row * I;
+    scale[ns] = n_live[ns] ? w_scale[row] : 0.f;
+  }
+
+  const int mt = (tile.rows + 15) / 16;
+  const bf16* a_rows[4];
+  bool a_live[4];
+#pragma unroll
+  for (int pm = 0; pm < 4; ++pm) {
+    const int m = pm * 16 + (lane & 15);
+    const int p = tile.row0 + m;
+    a_live[pm] = m < tile.rows && p < TK;
+    a_rows[pm] = act + (long)(a_live[pm] ? p : 0) * I;
+  }
+
+  moe_f32x4 acc[4][NSUB];
+#pragma unroll
+  for (int pm = 0; pm < 4; ++pm)
+#pragma unroll
+    for (int ns = 0; ns < NSUB; ++ns)
+      acc[pm][ns] = moe_f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int chunks_per_split = (I / MOE_KT) / SK;
+  const int k_begin = sk * chunks_per_split * MOE_KT;
+  moe_mma_stream_fp8<NSUB>(acc, a_rows, a_live, w_rows, n_live, mt, k_begin,
+                           k_begin + chunks_per_split * MOE_KT, lane);
+
+#pragma unroll
+  for (int pm = 0; pm < 4; ++pm) {
+    if (pm >= mt) break;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = pm * 16 + (lane >> 4) * 4 + i;
+      const int p = tile.row0 + m;
+      if (m >= tile.rows || p >= TK) continue;
+      const int slot = sorted_slots[p];
+      if (slot < 0 || slot >= TK) continue;
+      float* dst = ws + ((long)sk * TK + slot) * H;
+#pragma unroll
+      for (int ns = 0; ns < NSUB; ++ns) {
+        const int n_out = n0 + 16 * ns + (lane & 15);
+        if (n_out < H) dst[n_out] = scale[ns] * acc[pm][ns][i];
       }
     }
   }
@@ -721,10 +942,19 @@ extern "C" void launch_moe_route(int* topk_idx, float* topk_w,
 
 extern "C" void launch_moe_gate_up_swiglu(void* act, const void* x,
                                           const void* w,
+                                          const float* w_scale, int w_fp8,
                                           const int* expert_offsets,
                                           const int* sorted_slots, int T,
                                           int E, int top_k, int H, int I,
                                           int tiled, hipStream_t stream) {
+  if (w_fp8) {  // streaming family only: the caller refuses fp8 + tiled
+    dim3 grid((I + MOE_NT - 1) / MOE_NT, moe_num_m_tiles(T * top_k, E));
+    hipLaunchKernelGGL(moe_gate_up_swiglu_fp8_kernel, grid, dim3(256), 0,
+                       stream, (bf16*)act, (const bf16*)x, (const fp8_t*)w,
+                       w_scale, expert_offsets, sorted_slots, T, E, top_k, H,
+                       I);
+    return;
+  }
   if (tiled) {
     dim3 grid((I + MOE_TBN / 2 - 1) / (MOE_TBN / 2),
               moe_num_m_tiles_tiled(T * top_k, E));
@@ -742,6 +972,7 @@ extern "C" void launch_moe_gate_up_swiglu(void* act, const void* x,
 // tiled: num_splits must be 1 (the tiled kernel does not split K).
 extern "C" void launch_moe_down_combine(void* out, float* ws,
                                         const void* act, const void* w,
+                                        const float* w_scale, int w_fp8,
                                         const float* topk_w,
                                         const int* expert_offsets,
                                         const int* sorted_slots, int T,
@@ -749,7 +980,21 @@ extern "C" void launch_moe_down_combine(void* out, float* ws,
                                         int num_splits, int tiled,
                                         hipStream_t stream) {
   const int TK = T * top_k;
-  if (tiled) {
+  if (w_fp8) {  // streaming family only, same grid as the bf16 call
+    tiled = 0;
+    const int nsub = moe_down_nsub(TK);
+    const int nt = MOE_NT * nsub;
+    dim3 grid((H + nt - 1) / nt, moe_num_m_tiles(TK, E), num_splits);
+    if (nsub == 1) {
+      hipLaunchKernelGGL((moe_down_fp8_kernel<1>), grid, dim3(256), 0, stream,
+                         ws, (const bf16*)act, (const fp8_t*)w, w_scale,
+                         expert_offsets, sorted_slots, TK, E, H, I);
+    } else {
+      hipLaunchKernelGGL((moe_down_fp8_kernel<2>), grid, dim3(256), 0, stream,
+                         ws, (const bf16*)act, (const fp8_t*)w, w_scale,
+                         expert_offsets, sorted_slots, TK, E, H, I);
+    }
+  } else if (tiled) {
     dim3 grid((H + MOE_TBN - 1) / MOE_TBN, moe_num_m_tiles_tiled(TK, E));
     hipLaunchKernelGGL(moe_down_tiled_kernel, grid, dim3(256), 0, stream, ws,
                        (const bf16*)act, (const bf16*)w, expert_offsets,

@@ -612,6 +612,33 @@ int moe_tiled_arg(const c10::optional<std::string>& variant, long TK, long E) {
   return *variant == "tiled" ? 1 : 0;
 }
 
+// Stacked expert weights w [E, N, K]: bf16 without w_scale, or weight-only
+// fp8 (e4m3fn) with one float32 scale per (expert, row), w_scale [E, N].
+// Either without the other is refused, and so is fp8 on the tiled kernels,
+// which have no fp8 form. Returns the scale pointer, null for bf16.
+const float* check_moe_weights(const torch::Tensor& w,
+                               const c10::optional<torch::Tensor>& w_scale,
+                               const c10::optional<std::string>& variant,
+                               const char* name) {
+  if (!w_scale.has_value()) {
+    check_bf16_contig(w, name);  // fp8 weights without a scale end here
+    return nullptr;
+  }
+  TORCH_CHECK(w.is_cuda() && w.is_contiguous() &&
+                  w.scalar_type() == at::kFloat8_e4m3fn,
+              name, " must be contiguous float8_e4m3fn on GPU when a scale "
+              "is given");
+  TORCH_CHECK(w.dim() == 3, name, " must be [E, N, K]");
+  TORCH_CHECK(w_scale->is_cuda() && w_scale->is_contiguous() &&
+                  w_scale->scalar_type() == torch::kFloat &&
+                  w_scale->dim() == 2 && w_scale->size(0) == w.size(0) &&
+                  w_scale->size(1) == w.size(1),
+              name, " scale must be contiguous float32 [E, N] on GPU");
+  TORCH_CHECK(!variant.has_value() || *variant != "tiled",
+              "fp8 expert weights run the streaming kernels only");
+  return w_scale->data_ptr<float>();
+}
+
 // router_logits fp32 [T, E] → (topk_idx [T,K] i32, topk_w [T,K] f32,
 // expert_offsets [E+1] i32, sorted_slots [T*K] i32), all on device.
 std::vector<torch::Tensor> moe_route(torch::Tensor router_logits,
@@ -639,13 +666,16 @@ std::vector<torch::Tensor> moe_route(torch::Tensor router_logits,
 }
 
 // act_sorted [T*K, I] = silu(g)·u of x[token] · w_gate_up[e]^T, rows in
-// expert-sorted order. w_gate_up is the stacked [E, 2I, H] tensor.
+// expert-sorted order. w_gate_up is the stacked [E, 2I, H] tensor, bf16 or
+// e4m3 with w_scale [E, 2I] (check_moe_weights).
 torch::Tensor moe_gate_up_swiglu(torch::Tensor x, torch::Tensor w_gate_up,
                                  torch::Tensor expert_offsets,
                                  torch::Tensor sorted_slots, int64_t top_k,
-                                 c10::optional<std::string> variant) {
+                                 c10::optional<std::string> variant,
+                                 c10::optional<torch::Tensor> w_scale) {
   check_bf16_contig(x, "x");
-  check_bf16_contig(w_gate_up, "w_gate_up");
+  const float* scale_ptr =
+      check_moe_weights(w_gate_up, w_scale, variant, "w_gate_up");
   check_i32_contig(expert_offsets, "expert_offsets");
   check_i32_contig(sorted_slots, "sorted_slots");
   TORCH_CHECK(x.dim() == 2 && w_gate_up.dim() == 3,
@@ -664,7 +694,8 @@ torch::Tensor moe_gate_up_swiglu(torch::Tensor x, torch::Tensor w_gate_up,
               "sorted_slots must be [T*top_k]");
   auto act = torch::empty({T * top_k, I}, x.options());
   launch_moe_gate_up_swiglu(act.data_ptr(), x.data_ptr(),
-                            w_gate_up.data_ptr(),
+                            w_gate_up.data_ptr(), scale_ptr,
+                            scale_ptr ? 1 : 0,
                             expert_offsets.data_ptr<int>(),
                             sorted_slots.data_ptr<int>(), (int)T, (int)E,
                             (int)top_k, (int)H, (int)I,
@@ -677,14 +708,18 @@ torch::Tensor moe_gate_up_swiglu(torch::Tensor x, torch::Tensor w_gate_up,
 // w_down the stacked [E, H, I] tensor; split-K partials go through an
 // fp32 workspace indexed by slot and are summed in a fixed order. The
 // tiled kernels do not split K: their workspace is T·K·H floats, refused
-// above 1 GiB (the cap of the ragged extend workspace).
+// above 1 GiB (the cap of the ragged extend workspace). w_down is bf16 or
+// e4m3 with w_scale [E, H] (check_moe_weights); fp8 weights keep the
+// streaming kernels and their split count at every T.
 torch::Tensor moe_down_combine(torch::Tensor act_sorted, torch::Tensor w_down,
                                torch::Tensor topk_w,
                                torch::Tensor expert_offsets,
                                torch::Tensor sorted_slots,
-                               c10::optional<std::string> variant) {
+                               c10::optional<std::string> variant,
+                               c10::optional<torch::Tensor> w_scale) {
   check_bf16_contig(act_sorted, "act_sorted");
-  check_bf16_contig(w_down, "w_down");
+  const float* scale_ptr =
+      check_moe_weights(w_down, w_scale, variant, "w_down");
   check_i32_contig(expert_offsets, "expert_offsets");
   check_i32_contig(sorted_slots, "sorted_slots");
   TORCH_CHECK(topk_w.is_cuda() && topk_w.scalar_type() == torch::kFloat &&
@@ -704,7 +739,7 @@ torch::Tensor moe_down_combine(torch::Tensor act_sorted, torch::Tensor w_down,
   TORCH_CHECK(H % 16 == 0, "H (N-dim) must be a multiple of 16");
   TORCH_CHECK(expert_offsets.numel() == E + 1, "expert_offsets must be [E+1]");
   TORCH_CHECK(sorted_slots.numel() == T * K, "sorted_slots must be [T*K]");
-  const int tiled = moe_tiled_arg(variant, T * K, E);
+  const int tiled = scale_ptr ? 0 : moe_tiled_arg(variant, T * K, E);
   const int sk =
       tiled ? 1 : moe_down_num_splits((int)(T * K), (int)E, (int)H, (int)I);
   TORCH_CHECK(!tiled || T * K * H <= (1L << 28),
@@ -714,6 +749,7 @@ torch::Tensor moe_down_combine(torch::Tensor act_sorted, torch::Tensor w_down,
   auto out = torch::empty({T, H}, act_sorted.options());
   launch_moe_down_combine(out.data_ptr(), ws.data_ptr<float>(),
                           act_sorted.data_ptr(), w_down.data_ptr(),
+                          scale_ptr, scale_ptr ? 1 : 0,
                           topk_w.data_ptr<float>(),
                           expert_offsets.data_ptr<int>(),
                           sorted_slots.data_ptr<int>(), (int)T, (int)E,
@@ -824,12 +860,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Grouped gate_up GEMM + SwiGLU over expert-sorted rows",
         py::arg("x"), py::arg("w_gate_up"), py::arg("expert_offsets"),
         py::arg("sorted_slots"), py::arg("top_k"),
-        py::arg("variant") = py::none());
+        py::arg("variant") = py::none(), py::arg("w_scale") = py::none());
   m.def("moe_down_combine", &moe_down_combine,
         "Grouped down GEMM + deterministic top-k combine",
         py::arg("act_sorted"), py::arg("w_down"), py::arg("topk_w"),
         py::arg("expert_offsets"), py::arg("sorted_slots"),
-        py::arg("variant") = py::none());
+        py::arg("variant") = py::none(), py::arg("w_scale") = py::none());
   m.def("moe_down_splits", &moe_down_splits,
         "Split-K factor moe_down_combine uses for these static shapes",
         py::arg("tokens"), py::arg("top_k"), py::arg("num_experts"),
